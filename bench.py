@@ -8,7 +8,9 @@ labels) -> host GvdGraph, seeds / rows arrays and both OccupancyGrids in host me
 
 `value` = W*H / the median per-frame wall-clock of the sequential loop (one frame at a time, no overlap
 between frames: the timed region of the contract), i.e. BASELINE.md's "W.H / (seed-gen + GVD
-wall-clock per frame), median of >= 5 warm runs". Beside it, in the same run:
+wall-clock per frame), median of >= 5 warm runs". A plain run sets up, warms up, times the steps, writes the last
+timed step's outputs (--dump-outputs DIR) and prints the line. With --full, beside it and in the same run (and then
+the GVD pair-evaluation frame, the sustained seed-gen leg and the CPU baseline):
   pipelined       frames overlapped as the reference's two nodes overlap (seed-gen of frame k while
                   the GVDs of earlier frames run, --depth jobs in flight, next cloud prefetched):
                   throughput and frame latency;
@@ -20,7 +22,7 @@ own independent 4096^2 map (scene seed 3 + rank); no data-path collective; the b
 max-over-ranks time use torch.distributed (RCCL). --tiled: one map split into tiles over the ranks
 (SURVEY §8e, strong scaling). --tiled --stream: C4 over the ranks (BASELINE configs[4], 8 x MI355X
 streaming): every rank receives each scan and keeps its tile's points box in its own HBM map. With N > 1
-the same launch also reports the tiled C3 map (`tiled`) and the tiled C4 stream (`tiled_stream`).
+and --full the same launch also reports the tiled C3 map (`tiled`) and the tiled C4 stream (`tiled_stream`).
 """
 from __future__ import annotations
 
@@ -37,6 +39,10 @@ for sub in ("tools", "active-orchard-slam_amd"):
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
 WATCHDOG_EXIT = 3      # exit status of a run whose tiled section hung (its watchdog fired)
 TILED_ERROR_EXIT = 4   # exit status of a run whose tiled / tiled_stream section raised (after the main line)
+# --dump-outputs: at most DUMP_MAX_BYTES in all; a larger array is sampled at DUMP_MAX_ELEMS seeded flat indices
+DUMP_MAX_BYTES = 64 * 10**6
+DUMP_MAX_ELEMS = 1 << 22
+DUMP_SEED = 20240607
 # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE summaries (tools/pmc_traffic.py) of the ROR stage, per config,
 # for the kernels of this build's ROR design. A config or design without a committed PMC run gets null.
 ROR_DESIGN = "r06"    # (r04v: the host cloud split at upload; the partition passes read the front only. r05: + the tile
@@ -104,10 +110,53 @@ def parse(argv=None):
     ap.add_argument("--fixed-root", action="store_true",
                     help="--tiled: rank 0 finishes every frame (default: frame k's root is rank k mod N, so the "
                          "whole-map stages and the GVD jobs rotate over the ranks)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the line reports beside its value: the pipelined and "
+                         "device-resident loops, the GVD pair-evaluation frame, the sustained seed-gen leg, the CPU "
+                         "baseline and, with --gpus N > 1, the tiled C3 / C4 extras (each can be dropped with its "
+                         "--no-* option). Without --full a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the arrays the last timed step returned (the seed-gen frame and "
+                         "the GvdGraph) as DIR/<name>.npy, float32 or float64; an array of more than "
+                         f"{DUMP_MAX_ELEMS} elements is written as a fixed, seeded sample of its elements")
     a = ap.parse_args(argv)
     if a.config is None:
         a.config = "C3" if a.tiled and not a.stream else "C2"
+    if not a.full:
+        a.no_cpu_baseline = a.no_pipelined_rate = a.no_device_rate = a.no_tiled_rate = True
     return a
+
+
+def dump_outputs(directory: str, g: dict, gg) -> dict:
+    """--dump-outputs: the arrays of the last timed step's results (seed-gen dict g, graph dict gg) as
+    DIR/seedgen_<key>.npy and DIR/gvd_<key>.npy. float64 stays float64, 32-bit and wider integers become float64
+    (exact), everything else float32 (exact for 8 / 16-bit integers and float32). An array of more than
+    DUMP_MAX_ELEMS elements (the two OccupancyGrids at C2) is written as its elements at DUMP_MAX_ELEMS flat
+    indices drawn once from a generator seeded with DUMP_SEED and the array's size: the same cells in every run.
+    The arrays are copied at once: g and gg may hold views of library-owned buffers that the next call reuses.
+    Returns {file name: bytes}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    written, total = {}, 0
+    for prefix, d in (("seedgen", g), ("gvd", gg)):
+        for key, v in sorted((d or {}).items()):
+            if not isinstance(v, np.ndarray):
+                continue
+            flat = v.reshape(-1)
+            if flat.size > DUMP_MAX_ELEMS:
+                idx = np.sort(np.random.default_rng([DUMP_SEED, flat.size]).choice(flat.size, DUMP_MAX_ELEMS, replace=False))
+                out = flat[idx]
+            else:
+                out = v
+            wide = out.dtype == np.float64 or (out.dtype.kind in "iu" and out.dtype.itemsize >= 4)
+            out = np.array(out, dtype=np.float64 if wide else np.float32)   # (always a copy)
+            if total + out.nbytes > DUMP_MAX_BYTES:
+                raise RuntimeError(f"--dump-outputs: {prefix}_{key} would take the dump past {DUMP_MAX_BYTES} bytes")
+            name = f"{prefix}_{key}.npy"
+            np.save(os.path.join(directory, name), out)
+            written[name] = out.nbytes
+            total += out.nbytes
+    return written
 
 
 def timed_region(step, steps: int, warmup: int, world: int, sync, dist=None, device=None):
@@ -493,11 +542,12 @@ def run(a, E, dist, quiet=False):
             comm = aos_tiles.ThreadGroup(1).comm(0, plan["exchange_bytes"], dev)
     else:
         cloud = orchard.generate(cfg, seed=cfg.seed + rank)
-    d_cloud = torch.from_numpy(cloud).to(dev)
     n = cloud.shape[0]
     # the frame starts from the PointCloud2 bytes in host memory (a ROS message) and ends
     # with the OccupancyGrids in host memory. Stream / tiled modes start from their own HBM-resident maps.
     host_io = not (a.device_io or a.stream or a.tiled)
+    # (the HBM copy of the cloud: the device-resident modes' input, and --full's device-resident legs)
+    d_cloud = torch.from_numpy(cloud).to(dev) if (a.full or not host_io) else None
     h_cloud = cloud if host_io else None
     del cloud
     if a.stream:
@@ -685,6 +735,11 @@ def run(a, E, dist, quiet=False):
     g, gg = res[-1]
     if a.tiled:
         g, gg = pick_tiled_frames(res, g, gg)
+    dumped = None
+    if a.dump_outputs and rank == 0 and not quiet:
+        # (before any further call on the handle: the grids and the graph are views of library-owned buffers)
+        _progress(f"writing the last timed step's outputs to {a.dump_outputs}")
+        dumped = dump_outputs(a.dump_outputs, g, gg)
     cells = g["width"] * g["height"]
     units = (cells / 1e6) * (1 if a.tiled else world)   # Mcells per step over all ranks
     med = _median(per)
@@ -734,7 +789,7 @@ def run(a, E, dist, quiet=False):
         extra["device_resident"] = {"value": round(units / dmed, 3), "median_ms": round(dmed * 1e3, 3),
                                     "ms_per_step": round(ddt / a.steps * 1e3, 3),
                                     "io": "cloud already in HBM, OccupancyGrids left in HBM, GvdGraph + seeds to host"}
-    if not (a.stream or a.tiled):
+    if a.full and not (a.stream or a.tiled):
         # SURVEY §8d's GVD figure: the graph phase's "pair evaluations" (one counted frame outside the timed
         # region: the counts are a function of the frame's inputs; rates over the timed frames' graph phase)
         ctx.gvd_set_count_evals(True)
@@ -949,6 +1004,8 @@ def run(a, E, dist, quiet=False):
                 out["root_serial_split_ms"] = tiled_split
             if frame_lat:
                 out["frame_latency_ms"] = {"p50": round(_median(frame_lat), 2), "max": round(frame_lat[-1], 2)}
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": a.dump_outputs, "bytes": sum(dumped.values()), "files": sorted(dumped)}
         if child is not None:
             out["cpu_baseline"] = finish_cpu_baseline(child)
         elif world == 1 and not a.no_cpu_baseline and not a.stream:

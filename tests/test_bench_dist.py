@@ -201,6 +201,40 @@ def test_ror_points_read_mean_over_timed_frames():
     assert bench.ror_points_read([({}, None)], 7) == 7.0
 
 
+def test_plain_run_measures_only_the_timed_steps():
+    """Without --full every measurement beside the timed steps is off; --full turns them on, and each --no-*
+    option still drops its own."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.no_cpu_baseline and a.no_pipelined_rate and a.no_device_rate and a.no_tiled_rate
+    f = bench.parse(["--full"])
+    assert f.full and not (f.no_cpu_baseline or f.no_pipelined_rate or f.no_device_rate or f.no_tiled_rate)
+    f = bench.parse(["--full", "--no-cpu-baseline"])
+    assert f.no_cpu_baseline and not f.no_pipelined_rate
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: every array of the last step's results as float32 / float64 .npy, values kept exactly; an
+    array past the element limit as the same seeded sample in every run; scalars, timings and None skipped."""
+    big = (np.arange(bench.DUMP_MAX_ELEMS + 1000) % 251).astype(np.int8)
+    g = {"occupancy": big, "voronoi_seeds": np.array([[0.1, 0.2], [1e-9, 3.0]]), "width": 8, "ms": {"total": 1.0},
+         "d_occupancy": 12345}
+    gg = {"edges": np.array([[0, 1], [2**31 - 1, 3]], np.int32), "edge_lengths": np.array([0.5, 1.5], np.float32)}
+    w1 = bench.dump_outputs(str(tmp_path / "a"), g, gg)
+    w2 = bench.dump_outputs(str(tmp_path / "b"), g, gg)
+    assert sorted(w1) == ["gvd_edge_lengths.npy", "gvd_edges.npy", "seedgen_occupancy.npy", "seedgen_voronoi_seeds.npy"]
+    assert w1 == w2 and sum(w1.values()) <= bench.DUMP_MAX_BYTES
+    ld = {k: np.load(tmp_path / "a" / k) for k in w1}
+    assert ld["seedgen_voronoi_seeds.npy"].dtype == np.float64 and np.array_equal(ld["seedgen_voronoi_seeds.npy"], g["voronoi_seeds"])
+    assert ld["gvd_edges.npy"].dtype == np.float64 and np.array_equal(ld["gvd_edges.npy"], gg["edges"])
+    assert ld["gvd_edge_lengths.npy"].dtype == np.float32 and np.array_equal(ld["gvd_edge_lengths.npy"], gg["edge_lengths"])
+    occ = ld["seedgen_occupancy.npy"]
+    assert occ.dtype == np.float32 and occ.shape == (bench.DUMP_MAX_ELEMS,)
+    assert np.array_equal(occ, np.load(tmp_path / "b" / "seedgen_occupancy.npy"))
+    assert set(np.unique(occ)) <= set(np.unique(big).astype(np.float32)) and len(np.unique(occ)) > 100
+    assert bench.dump_outputs(str(tmp_path / "c"), {"root": False, "width": 8}, None) == {}
+
+
 def test_cpu_baseline_child_process():
     """The CPU baseline in its own process pinned to one core (started before the GPU is touched, told to start
     after the main timed region); this process keeps the other cores."""

@@ -14,15 +14,17 @@ import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-OUT = "/tmp/aos_sanitize"
 
 
 @pytest.fixture(scope="module")
-def built():
+def built(tmp_path_factory):
     if shutil.which("g++") is None:
         pytest.skip("no g++")
-    subprocess.run(["make", "-s", "-C", os.path.join(HERE, "sanitize"), f"OUT={OUT}"], check=True)
-    return OUT
+    # (a directory of this pytest run's own: a fixed one may hold another checkout's or another user's binaries)
+    out = str(tmp_path_factory.mktemp("aos_sanitize"))
+    subprocess.run(["make", "-s", "-j", str(min(8, os.cpu_count() or 1)), "-C", os.path.join(HERE, "sanitize"),
+                    f"OUT={out}"], check=True)
+    return out
 
 
 def _run(cmd, env=None, timeout=600):

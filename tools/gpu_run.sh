@@ -4,7 +4,7 @@
 # first failure):
 #   pytest   the -m gpu parity suite (PYTEST_K: a -k expression)
 #   smoke    __graft_entry__.smoke()
-#   bench    the default bench line (BENCH_ARGS, default --no-cpu-baseline)
+#   bench    the full bench line (BENCH_ARGS, default --full --no-cpu-baseline)
 #   stream   the C4 streaming bench
 #   kt       rocprofv3 --kernel-trace --stats of the sequential C2 loop
 #   ktc3     the same on one C3 frame set (bench --config C3 on one GPU)
@@ -22,6 +22,8 @@ set -e
 R=$PWD
 TAG=${TAG:-r04x}
 STEPS=${STEPS:-"pytest smoke bench kt"}
+# (the bench step reports the pipelined / device-resident figures beside the value: they are behind --full)
+BENCH_ARGS=${BENCH_ARGS:---full --no-cpu-baseline}
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 for step in $STEPS; do
@@ -125,13 +127,13 @@ for step in $STEPS; do
         > gpurun_out/${TAG}_ts1.log 2> gpurun_out/${TAG}_ts1.err || { tail -30 gpurun_out/${TAG}_ts1.err; exit 1; }
       grep '^{' gpurun_out/${TAG}_ts1.log | cut -c1-300
       AOS_BENCH_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-        --master-addr 127.0.0.1 --master-port 29631 bench.py --gpus 2 --steps 8 --warmup 3 --no-cpu-baseline \
+        --master-addr 127.0.0.1 --master-port 29631 bench.py --gpus 2 --steps 8 --warmup 3 --full --no-cpu-baseline \
         > gpurun_out/${TAG}_ts2.log 2>&1 || { tail -30 gpurun_out/${TAG}_ts2.log; exit 1; }
       grep '^{' gpurun_out/${TAG}_ts2.log | cut -c1-300 ;;
     rccl2)   # the driver's --gpus 2 flow over RCCL itself on the one GPU (AOS_BENCH_RCCL_SHARED_GPU: a NCCL_HOSTID per
              # rank, RCCL's socket transport on loopback): the independent maps, then the tiled C3 / C4 extras
       AOS_BENCH_RCCL_SHARED_GPU=1 timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-        --master-addr 127.0.0.1 --master-port 29651 bench.py --gpus 2 --steps 8 --warmup 2 --no-cpu-baseline \
+        --master-addr 127.0.0.1 --master-port 29651 bench.py --gpus 2 --steps 8 --warmup 2 --full --no-cpu-baseline \
         > gpurun_out/${TAG}_rccl2.log 2>&1 || { tail -30 gpurun_out/${TAG}_rccl2.log; exit 1; }
       grep '^{' gpurun_out/${TAG}_rccl2.log | cut -c1-400 ;;
     rccl6)   # the tiled C3 frame over 6 RCCL ranks on the one GPU (3 x 2 tiles: halo strips to neighbours only)
