@@ -127,6 +127,9 @@ struct aos_ctx {
     aos::FrameGeom geom{};                 // the whole map
     bool tiled_frame = false;
     int thin_iters = 0, thin_iters_prev = 0;   // (the previous frame's T sizes the first thinning batch)
+    // set while finish_frame runs ahead of the thinning flags: true once they show that thinning had not converged
+    // (SeedStageIn::stale)
+    std::function<bool()> frame_stale;
     // First thinning batch (n temporal-block launches; the opening, which clears the flags, runs just before it so the
     // inflated grid's read-back can be queued behind it) as hipGraphs, one per batch
     // size n (a power of two), captured on first use and replayed while every pointer and size baked into

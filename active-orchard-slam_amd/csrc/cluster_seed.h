@@ -128,6 +128,12 @@ struct SeedStageIn {
     // (nullable) the frameless skeleton's bits in host memory, WW words per row, once they are there (waits for
     // their read-back; returns null when they are not sent): the exact BFS replays walk them (cluster_host.cpp)
     std::function<const uint64_t *()> host_skel_bits;
+    // (nullable) asked once, after the stage's first host wait (the foreground count): true when the caller has
+    // learnt by then that this skeleton is not final (a frame run ahead of the thinning flags, which shows that
+    // thinning had not converged) and the result will be discarded: the stage returns an empty result at once.
+    // An unconverged skeleton can be a solid blob, one cluster of 10^5 - 10^6 cells, and k_cluster_stats' all-pairs
+    // branch on it alone took ~50 s (thinning).
+    std::function<bool()> stale;
 };
 
 struct GridC;

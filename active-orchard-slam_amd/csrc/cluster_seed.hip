@@ -834,6 +834,12 @@ void run_cluster_seed_stage(ClusterSeedState &S, const SeedStageIn &in, SeedStag
     S.h_rec.clear();
     S.n_replay_from_bits = S.n_replay_gpu = S.n_replay_cells = 0;
     std::vector<RowDev> rows;
+    if (!in.pre && in.stale && in.stale()) {   // the caller redoes the frame: an empty result, like a frame without rows
+        S.n_fg = 0;
+        S.n_rows = 0;
+        if (ev_mid) AOS_HIP(hipEventRecord(ev_mid, s));
+        return;
+    }
     if (in.pre) {   // labelled and measured by the tile ranks (cluster_dist.hip)
         S.h_rec = in.pre->rec;
         S.n_clusters = (int)S.h_rec.size();

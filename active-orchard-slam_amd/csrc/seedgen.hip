@@ -915,7 +915,16 @@ bool aos_ctx::run_seedgen_once(bool want_host, aos_seedgen_out &out, bool allow_
         AOS_HIP(hipEventRecord(ev[3], s));
         skel_bits = d_out;
         const double t_thin = since();
-        finish_frame(g, want_host, nullptr, out);   // (ends with a stream synchronisation: h_flags is on the host)
+        // (the cluster stage asks at its first host wait, when k_thin_pick's h_flags are on the host: a first batch
+        // that thinning outgrew leaves a skeleton that is not final, and its clusters are not worth computing)
+        frame_stale = [h_flags, launched, K] { return thin_iterations(h_flags, launched * K) == 0; };
+        try {
+            finish_frame(g, want_host, nullptr, out);   // (ends with a stream synchronisation: h_flags is on the host)
+        } catch (...) {
+            frame_stale = nullptr;
+            throw;
+        }
+        frame_stale = nullptr;
         if (thin_graph_check) thin_check_flags(d_flags, h_flags, 1 + launched * K, nflags);
         if (ror_collect()) return true;
         ror_done = true;
@@ -1126,6 +1135,7 @@ void aos_ctx::finish_frame(const FrameGeom &g, bool want_host, const uint64_t *c
                 return static_cast<const uint64_t *>(h_skel_bits.p);
             };
     }
+    sin.stale = frame_stale;
     SeedStageOut so;
     run_cluster_seed_stage(cs, sin, so, s, ev[4], trace_on() ? &ev[16] : nullptr);
     AOS_HIP(hipEventRecord(ev[5], s));
