@@ -131,6 +131,7 @@ void Subdiv2D::init_delaunay(float rx, float ry, float rw, float rh, int rect_mo
     const float big = 3.f * std::max(rw, rh);
     vp.clear(); vd.clear(); vfirst.clear(); vtype.clear(); rec.clear();
     recent = 0;
+    ho_valid = false;
     tlx = rx; tly = ry; brx = rx + rw; bry = ry + rh;
     vp.push_back(V2f{0.f, 0.f}); vd.push_back(V2d{0.0, 0.0, 0.0, 0, 0}); vfirst.push_back(0); vtype.push_back(-1);
     rec.push_back(Rec{});                                                      // quad-edge 0 (NULL)
@@ -202,6 +203,7 @@ int Subdiv2D::locate(float px, float py, int &out_edge, int &out_vertex) {
 
 bool Subdiv2D::insert(float x, float y) {
     int curr_edge = 0, curr_point = 0;
+    last_ho_slot = -1;
     const int loc = locate(x, y, curr_edge, curr_point);
     if (loc < 0) return false;        // PTLOC_ERROR (CV_StsBadSize) / outside rect (CV_StsOutOfRange)
     if (loc == 1) return true;        // existing vertex: nothing inserted
@@ -213,11 +215,14 @@ bool Subdiv2D::insert(float x, float y) {
     if (curr_edge == 0) return false;  // CV_Assert
     curr_point = new_point(x, y, 0);
     if (loc == 0 && !force_loop &&
-        (use_avx2 ? insert_cavity<true>(curr_edge, curr_point) : insert_cavity<false>(curr_edge, curr_point))) {
+        (use_ho     ? insert_cavity_ho(curr_edge, curr_point)
+         : use_avx2 ? insert_cavity<true>(curr_edge, curr_point)
+                    : insert_cavity<false>(curr_edge, curr_point))) {
         ++n_cavity;
         return true;
     }
     ++n_loop;
+    ho_valid = false;   // the swap loop leaves no ring arrays behind
     int base = new_edge();
     const int first_point = org(curr_edge);
     set_pts(base, first_point, curr_point);
@@ -458,6 +463,354 @@ bool Subdiv2D::insert_cavity(int e0, int p) {
     SDP_ADD(t_write, t_wr);
     return true;
 }
+
+// ---- hand-over: the previous insert's star as arrays (subdiv2d.h) ----
+#if defined(__x86_64__)
+#ifndef AOS_HO_VEC
+#define AOS_HO_VEC 1   // 0: every hand-over test and copy one slot at a time (the A/B of DESIGN.md 6.1)
+#endif
+static constexpr int HO_PAD = 4;   // spare entries before slot 0 and after slot cap - 1 (one of each is the cyclic copy)
+
+Subdiv2D::RingP Subdiv2D::ring_ptrs(Ring &r) {
+    return RingP{r.bd.data() + HO_PAD, r.bu.data() + HO_PAD, r.ba.data() + HO_PAD, r.sp.data() + HO_PAD,
+                 r.x.data() + HO_PAD,  r.y.data() + HO_PAD,  r.n.data() + HO_PAD,  r.ax.data() + HO_PAD,
+                 r.ay.data() + HO_PAD, r.an.data() + HO_PAD};
+}
+
+void Subdiv2D::ring_reserve(Ring &r, int slots) {   // keeps the contents
+    if (slots <= r.cap) return;
+    const int cap = std::max(256, 2 * slots);
+    const size_t n = (size_t)cap + 2 * HO_PAD;
+    r.bd.resize(n); r.bu.resize(n); r.ba.resize(n); r.sp.resize(n);
+    r.x.resize(n); r.y.resize(n); r.n.resize(n); r.ax.resize(n); r.ay.resize(n); r.an.resize(n);
+    r.cap = cap;
+}
+
+// ring_pass reading the spokes from the ring's own array (sp[k] = S_k, with bd / sp padded cyclically at m); it also
+// leaves slot k in the spare int of L_k's half record, which is how the next insert finds its fan triangle's slot.
+__attribute__((noinline)) static void ring_pass_ho(int *__restrict R, int *__restrict vfirst, const int *__restrict bd,
+                                                   const int *__restrict bu, const int *__restrict sp, int m, int p) {
+    int Sm = sp[m - 1], S = sp[0];
+    for (int k = 0; k < m; ++k) {
+        const int L = bd[k], Ln = bd[k + 1], x = bu[k], Sn = sp[k + 1];
+        const int sLn = Ln ^ 2, sS = S ^ 2;
+        R[2 * (ptrdiff_t)L] = S;                                       // Onext(L_k) = S_k
+        R[2 * (ptrdiff_t)L + 3] = k;                                   // slot of L_k
+        R[2 * (ptrdiff_t)sLn + 1] = S;                                 // Oprev(Sym L_k+1) = S_k
+        int *a = R + 2 * (ptrdiff_t)S, *b = R + 2 * (ptrdiff_t)sS;
+        a[0] = sLn; a[1] = L; a[2] = x;                                // S_k: x_k -> p
+        b[0] = Sm ^ 2; b[1] = Sn ^ 2; b[2] = p;                        // Sym S_k: around p, counter-clockwise
+        vfirst[x] = S;
+        Sm = S; S = Sn;
+    }
+}
+
+// The generic pre-order walk of insert_cavity from one link edge e, with a stack of its own; every leaf goes into
+// ring N at slot q with its apex and both vertices' coordinates. Returns the next free slot, or -1 when an apex is
+// already a cavity vertex; the last swap (or last_flip, if there was none) is left in ho_lf.
+__attribute__((noinline)) int Subdiv2D::ho_walk(int e, const V2d &Pin, int sA, Ring &N, int q, int last_flip) {
+    const V2d P = Pin;
+    auto area = [](const V2d &a, const V2d &b, const V2d &c) { return (b.x - a.x) * (c.y - a.y) - (b.y - a.y) * (c.x - a.x); };
+    int *const stk = dfs_stack.data();
+    int *top = stk;
+    RingP n = ring_ptrs(N);
+    int cap = N.cap;
+    for (;;) {
+        SDP_INC(dfs_steps);
+        const int t = oprev(e), w = dst(t), o = org(e);
+        const V2d &T = vd[w], &O = vd[o], &D = vd[dst(e)];
+        const double aTDO = area(T, D, O);   // same expressions and order as swap_loop
+        double val = T.n2 * area(D, P, O);
+        val -= D.n2 * area(T, P, O);
+        val += P.n2 * aTDO;
+        val -= O.n2 * area(T, D, P);
+        if ((aTDO > 0) & (val < -(FLT_EPSILON * 0.125))) {
+            V2d &W = vd[w];
+            if (W.stamp == sA) return -1;
+            W.stamp = sA;
+            W.spoke = e;                                       // e becomes w -> p
+            last_flip = e;
+            *top++ = t;                                        // u -> w, after the w -> v subtree
+            e = sym(onext(sym(e)));                            // w -> v
+            continue;
+        }
+        if (q >= cap) { ring_reserve(N, q + 1); n = ring_ptrs(N); cap = N.cap; }
+        n.bd[q] = e; n.bu[q] = o; n.ba[q] = w; n.sp[q] = O.spoke;
+        n.x[q] = O.x; n.y[q] = O.y; n.n[q] = O.n2;
+        n.ax[q] = T.x; n.ay[q] = T.y; n.an[q] = T.n2;
+        ++q;
+        if (top == stk) break;
+        e = *--top;
+    }
+    ho_lf = last_flip;
+    return q;
+}
+
+namespace {
+struct HoV { __m256d x, y, n; };
+AOS_AVX2 inline HoV ho_ld(const double *x, const double *y, const double *n, int i) {
+    return HoV{_mm256_loadu_pd(x + i), _mm256_loadu_pd(y + i), _mm256_loadu_pd(n + i)};
+}
+// four flip tests (bit i = lane i swaps); every lane runs swap_loop's subtractions, products and sums in its order
+AOS_AVX2 inline int ho_test4(const HoV &T, const HoV &O, const HoV &D, const HoV &P) {
+    const __m256d aTDO = area4(T.x, T.y, D.x, D.y, O.x, O.y);
+    __m256d val = _mm256_mul_pd(T.n, area4(D.x, D.y, P.x, P.y, O.x, O.y));
+    val = _mm256_sub_pd(val, _mm256_mul_pd(D.n, area4(T.x, T.y, P.x, P.y, O.x, O.y)));
+    val = _mm256_add_pd(val, _mm256_mul_pd(P.n, aTDO));
+    val = _mm256_sub_pd(val, _mm256_mul_pd(O.n, area4(T.x, T.y, D.x, D.y, P.x, P.y)));
+    const __m256d right = _mm256_cmp_pd(aTDO, _mm256_setzero_pd(), _CMP_GT_OQ);
+    const __m256d inside = _mm256_cmp_pd(val, _mm256_set1_pd(-(FLT_EPSILON * 0.125)), _CMP_LT_OQ);
+    return _mm256_movemask_pd(_mm256_and_pd(right, inside));
+}
+struct HoS { double x, y, n; };
+inline bool ho_test1(const HoS &T, const HoS &O, const HoS &D, const HoS &P) {
+    auto area = [](const HoS &a, const HoS &b, const HoS &c) { return (b.x - a.x) * (c.y - a.y) - (b.y - a.y) * (c.x - a.x); };
+    const double aTDO = area(T, D, O);
+    double val = T.n * area(D, P, O);
+    val -= D.n * area(T, P, O);
+    val += P.n * aTDO;
+    val -= O.n * area(T, D, P);
+    return (aTDO > 0) & (val < -(FLT_EPSILON * 0.125));
+}
+}  // namespace
+
+// Walk of the three roots when p lies in the fan triangle (x_k, x_k-1, c) of the previous star O (subdiv2d.h): the
+// roots are L_k (link), S_k-1 (descending chain) and Sym S_k (ascending chain); shift rotates the order
+// (ascending, descending, link) to the walk order eA, eB, e0. Writes the new ring into N; false: bail out.
+AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, int c, int sA, int &q_out) {
+    const RingP o = ring_ptrs(Oring);
+    RingP n = ring_ptrs(N);
+    const int m = Oring.m;
+    V2d *const V = vd.data();
+    const V2d Pv = V[p], Cv = V[c];
+    const HoS Ps{Pv.x, Pv.y, Pv.n2}, Cs{Cv.x, Cv.y, Cv.n2};
+    const HoV P4{_mm256_set1_pd(Pv.x), _mm256_set1_pd(Pv.y), _mm256_set1_pd(Pv.n2)};
+    const HoV C4{_mm256_set1_pd(Cv.x), _mm256_set1_pd(Cv.y), _mm256_set1_pd(Cv.n2)};
+    int q = 0, lf = -1;
+    const int km1 = k ? k - 1 : m - 1;
+
+#define HO_ROOM(cnt) do { if (q + (cnt) > N.cap) { ring_reserve(N, q + (cnt)); n = ring_ptrs(N); } } while (0)
+#define HO_XS(i) HoS{o.x[i], o.y[i], o.n[i]}
+#define HO_AS(i) HoS{o.ax[i], o.ay[i], o.an[i]}
+// a swap onto ring vertex v (the apex), whose spoke becomes s
+#define HO_SWAP(v, s) do { V2d &W_ = V[v]; if (W_.stamp == sA) return false; W_.stamp = sA; W_.spoke = (s); lf = (s); } while (0)
+// link slot j: a leaf is copied from the old ring (its right triangle is untouched), a swap leaves the star
+#define HO_LINK(j, swaps) do { \
+        if (swaps) { \
+            q = ho_walk(o.bd[j], Pv, sA, N, q, lf); \
+            if (q < 0) return false; \
+            lf = ho_lf; n = ring_ptrs(N); \
+        } else { \
+            HO_ROOM(1); \
+            n.bd[q] = o.bd[j]; n.bu[q] = o.bu[j]; n.ba[q] = o.ba[j]; n.sp[q] = V[o.bu[j]].spoke; \
+            n.x[q] = o.x[j]; n.y[q] = o.y[j]; n.n[q] = o.n[j]; n.ax[q] = o.ax[j]; n.ay[q] = o.ay[j]; n.an[q] = o.an[j]; \
+            ++q; \
+        } } while (0)
+// link slots j .. j + 3, all leaves: one copy per array (the spokes are the caller's)
+#define HO_COPY4(j) do { \
+        _mm_storeu_si128((__m128i *)(n.bd + q), _mm_loadu_si128((const __m128i *)(o.bd + (j)))); \
+        _mm_storeu_si128((__m128i *)(n.bu + q), _mm_loadu_si128((const __m128i *)(o.bu + (j)))); \
+        _mm_storeu_si128((__m128i *)(n.ba + q), _mm_loadu_si128((const __m128i *)(o.ba + (j)))); \
+        _mm256_storeu_pd(n.x + q, _mm256_loadu_pd(o.x + (j)));   _mm256_storeu_pd(n.y + q, _mm256_loadu_pd(o.y + (j))); \
+        _mm256_storeu_pd(n.n + q, _mm256_loadu_pd(o.n + (j)));   _mm256_storeu_pd(n.ax + q, _mm256_loadu_pd(o.ax + (j))); \
+        _mm256_storeu_pd(n.ay + q, _mm256_loadu_pd(o.ay + (j))); _mm256_storeu_pd(n.an + q, _mm256_loadu_pd(o.an + (j))); \
+    } while (0)
+
+    for (int r = 0; r < 3; ++r) {
+        const int kind = (r + shift) % 3;   // 0 ascending, 1 descending, 2 link
+        if (kind == 2) {
+            SDP_INC(dfs_steps);
+            const bool f = ho_test1(HO_AS(k), HO_XS(k), HO_XS(k - 1), Ps);
+            HO_LINK(k, f);
+        } else if (kind == 1) {
+            // S_j = x_j -> c for j = k - 1, k - 2, ...: T = x_j-1, O = x_j, D = c; a swap stacks L_j and goes on to S_j-1
+            int j = km1, nsw = 0;
+            for (;;) {
+                if (AOS_HO_VEC && j >= 3) {
+                    const int b = j - 3;   // lanes: slots b .. j
+                    int mask = ho_test4(ho_ld(o.x, o.y, o.n, b - 1), ho_ld(o.x, o.y, o.n, b), C4, P4);
+#ifdef AOS_SD_PROF
+                    g_sdprof.dfs_steps += 4;
+#endif
+                    if (mask == 0xf) {
+                        for (int i = 3; i >= 0; --i) HO_SWAP(o.bu[b - 1 + i], o.sp[b + i]);
+                        nsw += 4;
+                        j = b ? b - 1 : m - 1;
+                        continue;
+                    }
+                    while (mask & 8) { HO_SWAP(o.bu[j - 1], o.sp[j]); --j; ++nsw; mask <<= 1; }
+                    break;
+                }
+                SDP_INC(dfs_steps);
+                const int jm = j ? j - 1 : m - 1;
+                if (!ho_test1(HO_XS(jm), HO_XS(j), Cs, Ps)) break;
+                HO_SWAP(o.bu[jm], o.sp[j]);
+                ++nsw;
+                j = jm;
+            }
+            // the leaf S_j (apex x_j-1), then the stacked links L_j+1 .. L_k-1
+            HO_ROOM(1);
+            n.bd[q] = o.sp[j]; n.bu[q] = o.bu[j]; n.ba[q] = o.bu[j - 1]; n.sp[q] = V[o.bu[j]].spoke;
+            n.x[q] = o.x[j]; n.y[q] = o.y[j]; n.n[q] = o.n[j]; n.ax[q] = o.x[j - 1]; n.ay[q] = o.y[j - 1]; n.an[q] = o.n[j - 1];
+            ++q;
+            int i = j + 1 == m ? 0 : j + 1;
+            for (int cnt = nsw; cnt > 0;) {
+                if (AOS_HO_VEC && cnt >= 4 && i + 4 <= m) {
+                    const int mask = ho_test4(ho_ld(o.ax, o.ay, o.an, i), ho_ld(o.x, o.y, o.n, i), ho_ld(o.x, o.y, o.n, i - 1), P4);
+#ifdef AOS_SD_PROF
+                    g_sdprof.dfs_steps += 4;
+#endif
+                    if (mask == 0) {
+                        HO_ROOM(4);
+                        HO_COPY4(i);
+                        _mm_storeu_si128((__m128i *)(n.sp + q), _mm_loadu_si128((const __m128i *)(o.sp + i + 1)));   // x_i took S_i+1
+                        q += 4;
+                    } else {
+                        for (int l = 0; l < 4; ++l) HO_LINK(i + l, (mask >> l) & 1);
+                    }
+                    i += 4; cnt -= 4;
+                    if (i == m) i = 0;
+                } else {
+                    SDP_INC(dfs_steps);
+                    const bool f = ho_test1(HO_AS(i), HO_XS(i), HO_XS(i - 1), Ps);
+                    HO_LINK(i, f);
+                    i = i + 1 == m ? 0 : i + 1; --cnt;
+                }
+            }
+            if (nsw) n.sp[q - 1] = V[o.bu[km1]].spoke;   // the last link's origin x_k-1 is a root
+        } else {
+            // Sym S_j = c -> x_j for j = k, k + 1, ...: T = x_j+1, O = c, D = x_j; a swap walks L_j+1 at once, then Sym S_j+1
+            int j = k;
+            for (;;) {
+                if (AOS_HO_VEC && j + 4 <= m - 1) {
+                    const HoV X0 = ho_ld(o.x, o.y, o.n, j), X1 = ho_ld(o.x, o.y, o.n, j + 1);
+                    const int smask = ho_test4(X1, C4, X0, P4);
+                    const int lmask = ho_test4(ho_ld(o.ax, o.ay, o.an, j + 1), X1, X0, P4);   // links j + 1 .. j + 4
+#ifdef AOS_SD_PROF
+                    g_sdprof.dfs_steps += 8;
+#endif
+                    if (smask == 0xf && lmask == 0) {
+                        for (int i = 0; i < 4; ++i) HO_SWAP(o.bu[j + 1 + i], o.sp[j + i] ^ 2);
+                        HO_ROOM(4);
+                        HO_COPY4(j + 1);
+                        _mm_storeu_si128((__m128i *)(n.sp + q),
+                                         _mm_xor_si128(_mm_loadu_si128((const __m128i *)(o.sp + j)), _mm_set1_epi32(2)));   // x_j+1 took Sym S_j
+                        q += 4;
+                        j += 4;
+                        continue;
+                    }
+                    int i = 0;
+                    for (; i < 4 && ((smask >> i) & 1); ++i) {
+                        HO_SWAP(o.bu[j + 1], o.sp[j] ^ 2);
+                        HO_LINK(j + 1, (lmask >> i) & 1);
+                        ++j;
+                    }
+                    if (i < 4) break;
+                    continue;
+                }
+                SDP_INC(dfs_steps);
+                const int jn = j + 1 == m ? 0 : j + 1;
+                if (!ho_test1(HO_XS(jn), Cs, HO_XS(j), Ps)) break;
+                HO_SWAP(o.bu[jn], o.sp[j] ^ 2);
+                SDP_INC(dfs_steps);
+                const bool f = ho_test1(HO_AS(jn), HO_XS(jn), HO_XS(j), Ps);
+                HO_LINK(jn, f);
+                j = jn;
+            }
+            // the leaf Sym S_j (apex x_j+1)
+            HO_ROOM(1);
+            n.bd[q] = o.sp[j] ^ 2; n.bu[q] = c; n.ba[q] = o.bu[j + 1]; n.sp[q] = Cv.spoke;
+            n.x[q] = Cv.x; n.y[q] = Cv.y; n.n[q] = Cv.n2; n.ax[q] = o.x[j + 1]; n.ay[q] = o.y[j + 1]; n.an[q] = o.n[j + 1];
+            ++q;
+        }
+    }
+#undef HO_ROOM
+#undef HO_XS
+#undef HO_AS
+#undef HO_SWAP
+#undef HO_LINK
+#undef HO_COPY4
+    ho_lf = lf;
+    q_out = q;
+    return true;
+}
+
+// insert_cavity with the hand-over: the same walk, started either through the previous star's arrays (ho_fast) or,
+// when p does not lie in a fan triangle of the previous insert, from the three roots by ho_walk; both leave the new
+// star's ring in the other buffer.
+bool Subdiv2D::insert_cavity_ho(int e0, int p) {
+    if (++stamp >= (1 << 29)) { for (V2d &x : vd) x.stamp = 0; stamp = 1; }
+    const int sA = 2 * stamp;
+    const int eB = lnext(e0), eA = lnext(eB);          // root link edges in walk order: eA, eB, e0
+    if (lnext(eA) != e0) return false;
+    const int first = org(e0), v1 = org(eB), v2 = org(eA);
+    if (first == v1 || v1 == v2 || v2 == first) return false;
+    const size_t cap = vp.size() + 8;
+    if (dfs_stack.size() < cap) dfs_stack.resize(2 * cap);
+    // the quad-edges the three new_edge() calls below will hand out, so that the roots' spokes are known to the walk
+    int cn[3];
+    {
+        int f = free_q, fresh = (int)rec.size();
+        for (int i = 0; i < 3; ++i) {
+            if (f > 0) { cn[i] = 4 * f; f = rec[f].h[0].x; }
+            else cn[i] = 4 * fresh++;
+        }
+    }
+    V2d &F = vd[first], &A = vd[v1], &B = vd[v2];
+    F.stamp = A.stamp = B.stamp = sA;
+    F.spoke = cn[0]; A.spoke = cn[1]; B.spoke = cn[2];           // first -> p, v1 -> p, v2 -> p
+    const V2d P = vd[p];
+    Ring &O = ho[ho_cur], &N = ho[ho_cur ^ 1];
+    ring_reserve(N, 8);
+    int q = 0, lf = -1;
+    SDP_T0(t_dfs);
+    // the guard: a corner is the previous centre, and the opposite root is the link edge of the slot it carries
+    int shift = -1, L = 0, asc = 0, desc = 0;
+    if (ho_valid) {
+        const int c = ho_c;
+        if (v2 == c) { shift = 0; asc = eA; desc = eB; L = e0; }
+        else if (v1 == c) { shift = 2; L = eA; asc = eB; desc = e0; }
+        else if (first == c) { shift = 1; desc = eA; L = eB; asc = e0; }
+    }
+    bool fast = false;
+    if (shift >= 0) {
+        const int k = ri()[2 * (ptrdiff_t)L + 3];
+        const RingP o = ring_ptrs(O);
+        if ((unsigned)k < (unsigned)O.m && o.bd[k] == L && (o.sp[k] ^ 2) == asc && o.sp[k - 1] == desc) {
+            fast = true;
+            last_ho_slot = k; last_ho_ring = O.m;
+            if (!ho_fast(O, N, k, shift, p, ho_c, sA, q)) { ++n_ho_bail; ho_valid = false; last_ho_slot = -1; return false; }
+            lf = ho_lf;
+        }
+    }
+    if (!fast) {
+        if ((q = ho_walk(eA, P, sA, N, 0, -1)) < 0 || (q = ho_walk(eB, P, sA, N, q, ho_lf)) < 0 ||
+            (q = ho_walk(e0, P, sA, N, q, ho_lf)) < 0) {
+            ho_valid = false;
+            return false;
+        }
+        lf = ho_lf;
+    }
+    SDP_ADD(t_dfs, t_dfs);
+    SDP_T0(t_wr);
+    const int m = q;
+    const RingP n = ring_ptrs(N);   // (cap >= m, and HO_PAD spare entries follow)
+    N.m = m;
+    n.bd[m] = n.bd[0]; n.bu[m] = n.bu[0]; n.sp[m] = n.sp[0]; n.x[m] = n.x[0]; n.y[m] = n.y[0]; n.n[m] = n.n[0];
+    n.bd[-1] = n.bd[m - 1]; n.bu[-1] = n.bu[m - 1]; n.sp[-1] = n.sp[m - 1];
+    n.x[-1] = n.x[m - 1]; n.y[-1] = n.y[m - 1]; n.n[-1] = n.n[m - 1];
+    const int c0 = new_edge(), c1 = new_edge(), c2 = new_edge();   // first -> p, v1 -> p, v2 -> p (= cn[0 .. 2])
+    (void)c0; (void)c1;
+    vfirst[p] = sym(lf >= 0 ? lf : c2);   // the last setEdgePoints with p as destination
+    ring_pass_ho(ri(), vfirst.data(), n.bd, n.bu, n.sp, m, p);
+    ho_cur ^= 1; ho_c = p; ho_valid = true;
+    n_handover += fast;
+    SDP_ADD(t_write, t_wr);
+    return true;
+}
+#else
+bool Subdiv2D::insert_cavity_ho(int e0, int p) { return insert_cavity<false>(e0, p); }
+#endif
 
 bool Subdiv2D::same_state(const Subdiv2D &o) const {
     if (rec.size() != o.rec.size() || vp.size() != o.vp.size() || recent != o.recent || free_q != o.free_q ||

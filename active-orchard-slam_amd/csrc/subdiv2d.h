@@ -33,11 +33,23 @@
 //     (link) edges fixes; the unique onext/oprev values are stored directly.
 // The swap loop stays as the reference path (on-edge inserts, and any walk that meets an apex that is
 // already a cavity vertex). tools/sdcheck compares the two paths' complete state after every insert.
+//
+// Hand-over (insert_cavity_ho, on by default where the CPU has AVX2). On seed rows nearly every point lands in a
+// fan triangle of the previous insert's star, and nearly all of the walk's tests lie in that star or on its ring.
+// Each cavity insert therefore leaves its ring behind as arrays (struct Ring: per slot k in walk order the link
+// edge L_k = x_k -> x_k-1, its origin, the apex of its untouched right triangle, the spoke S_k = x_k -> centre, and
+// the double coordinates and |.|^2 of x_k and of the apex, padded cyclically), and the next insert walks the star
+// through them: the same tests with the same operands in the same order, four slots at a time, without following
+// oprev / dst / vertex loads, and the new ring is copied from the old one in runs. A spoke's ring links (ring_pass):
+//   Oprev(S_j) = L_j,  Oprev(Sym S_j) = Sym S_j+1,  Sym Onext(Sym S_j) = S_j-1,  Sym Onext(S_j) = L_j+1.
+// A link edge that swaps leaves the star: the generic walk runs from it. All of this state is per instance.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <functional>
 #include <vector>
+
+#define AOS_SD_HANDOVER 1   // set_handover(), n_handover and n_ho_bail exist (tools/sdcheck/sdprof.cpp)
 
 namespace aos {
 
@@ -55,6 +67,8 @@ class Subdiv2D {
     // 0: cavity DFS + bulk write (default); 1: always OpenCV's swap loop (reference / cross-check)
     void set_swap_loop(bool on) { force_loop = on; }
     void set_simd(bool on) { use_avx2 = on && simd_ok(); }   // batched boundary flip tests on AVX2 (off by default)
+    // walk the previous insert's star through the arrays it left (see above); needs AVX2, else the generic walk runs
+    void set_handover(bool on) { use_ho = on && simd_ok(); ho_valid = false; }
     static bool simd_ok() {
 #if defined(__x86_64__)
         return __builtin_cpu_supports("avx2");
@@ -65,6 +79,9 @@ class Subdiv2D {
     // full internal state (for the equivalence checker): rings, end points, firstEdge, recentEdge
     bool same_state(const Subdiv2D &o) const;
     long n_cavity = 0, n_loop = 0;   // inserts done by each path
+    long n_handover = 0;             // cavity inserts that walked the previous star's arrays (part of n_cavity)
+    long n_ho_bail = 0;              // hand-over walks that met a cavity vertex twice: redone by the swap loop
+    int last_ho_slot = -1, last_ho_ring = 0;   // the last insert's fan-triangle slot and ring length (-1: no hand-over)
     // getVoronoiFacetList(idx = {}): per real vertex (in vertex order) the facet polygon.
     // Emits the reference's edge list directly: (p_i, p_{i+1 mod n}) for facets with >= 2 points
     // (voronoi_diagram.cpp:97-114), as float x0, y0, x1, y1. Host reference of the GPU builder.
@@ -91,7 +108,8 @@ class Subdiv2D {
     // A quad-edge's record holds its two primal directed edges, 16 bytes each: directed edge e (always even, 4q or
     // 4q + 2) sits at byte 8 e of the array, so a field is one load at [base + 8 e + field] with no index arithmetic
     // (round 5: the replay's field accessors took 3-4 instructions each in the {on[2], op[2], org[2]} layout)
-    struct alignas(16) Half { int on, op, org, x; };   // x: the free-list link in half 0 of a free record
+    struct alignas(16) Half { int on, op, org, x; };   // x: the free-list link in half 0 of a free record;
+                                                       // in a live half: its slot in the last ring it bounded (hand-over)
     struct alignas(32) Rec { Half h[2]; };
     struct V2f { float x, y; };
     struct alignas(32) V2d { double x, y, n2; int stamp, spoke; };   // stamp / spoke: insert_cavity scratch
@@ -106,6 +124,16 @@ class Subdiv2D {
     // vertex (V2d) the spoke, valid while its stamp is this insert's
     std::vector<int> dfs_stack, cav_bnd, cav_bu;
     int stamp = 0;
+    // hand-over state: two ring buffers that alternate (ho[ho_cur] describes the star of vertex ho_c while ho_valid)
+    struct Ring {
+        std::vector<int> bd, bu, ba, sp;
+        std::vector<double> x, y, n, ax, ay, an;
+        int cap = 0, m = 0;
+    };
+    struct RingP { int *bd, *bu, *ba, *sp; double *x, *y, *n, *ax, *ay, *an; };   // slot 0 of each array
+    Ring ho[2];
+    int ho_cur = 0, ho_c = 0, ho_lf = -1;
+    bool ho_valid = false, use_ho = simd_ok();
     float tlx = 0, tly = 0, brx = 0, bry = 0;
 
     static int sym(int e) { return e ^ 2; }
@@ -139,6 +167,11 @@ class Subdiv2D {
     void flip_tests_scalar(const int *es, int n, const V2d &P, int *out) const;
     void flip_tests_avx2(const int *es, int n, const V2d &P, int *out) const;
     template <bool SIMD> bool insert_cavity(int e0, int curr_point);
+    static RingP ring_ptrs(Ring &r);
+    static void ring_reserve(Ring &r, int slots);
+    bool insert_cavity_ho(int e0, int curr_point);
+    int ho_walk(int e, const V2d &P, int sA, Ring &N, int q, int last_flip);
+    bool ho_fast(Ring &O, Ring &N, int k, int shift, int p, int c, int sA, int &q_out);
     void calc_voronoi();   // calcVoronoi on the exported layout (qx), creating the virtual vertices
     int facet_next(int e) const;
 };

@@ -24,11 +24,12 @@ static double uni() { return (splitmix() >> 11) * (1.0 / 9007199254740992.0); }
 
 struct Case { const char *name; std::vector<double> s; double b[4]; };
 
-static bool check(const Case &c, bool verbose, bool simd) {
+static bool check(const Case &c, bool verbose, bool simd, bool handover) {
     float rx = (float)(c.b[0] - 1.0), ry = (float)(c.b[2] - 1.0);
     float rw = (float)(std::abs(c.b[1] - c.b[0]) + 2.0), rh = (float)(std::abs(c.b[3] - c.b[2]) + 2.0);
     aos::Subdiv2D a, r;
     a.set_simd(simd);
+    a.set_handover(handover);
     r.set_swap_loop(true);
     const int n = (int)c.s.size() / 2;
     a.reserve(n); r.reserve(n);
@@ -48,11 +49,13 @@ static bool check(const Case &c, bool verbose, bool simd) {
         printf("FAIL %s: facet edges differ\n", c.name);
         return false;
     }
-    if (verbose) printf("ok   %-22s n=%-7d cavity inserts %ld, swap-loop inserts %ld\n", c.name, n, a.n_cavity, a.n_loop);
+    if (verbose)
+        printf("ok   %-22s n=%-7d cavity inserts %ld (hand-over %ld, bailed out %ld), swap-loop inserts %ld\n", c.name, n, a.n_cavity,
+               a.n_handover, a.n_ho_bail, a.n_loop);
     return true;
 }
 
-static double time_inserts(const Case &c, bool loop, bool simd, uint64_t &hash) {
+static double time_inserts(const Case &c, bool loop, bool simd, bool handover, uint64_t &hash) {
     float rx = (float)(c.b[0] - 1.0), ry = (float)(c.b[2] - 1.0);
     float rw = (float)(std::abs(c.b[1] - c.b[0]) + 2.0), rh = (float)(std::abs(c.b[3] - c.b[2]) + 2.0);
     const int n = (int)c.s.size() / 2;
@@ -61,6 +64,7 @@ static double time_inserts(const Case &c, bool loop, bool simd, uint64_t &hash) 
         aos::Subdiv2D sd;
         sd.set_swap_loop(loop);
         sd.set_simd(simd);
+        sd.set_handover(handover);
         sd.reserve(n);
         auto t0 = std::chrono::steady_clock::now();
         sd.init_delaunay(rx, ry, rw, rh, 0);
@@ -137,18 +141,21 @@ int main(int argc, char **argv) {
     }
     int fails = 0;
     const bool simd = aos::Subdiv2D::simd_ok();
-    for (int pass = 0; pass < (simd ? 2 : 1); ++pass) {
-        for (size_t i = 0; i < cases.size(); ++i) fails += !check(cases[i], pass == 0 && (i < 6 || i + 1 == cases.size()), pass == 0 && simd);
-        printf("%zu cases (%s flip tests), %d failed so far\n", cases.size(), pass == 0 && simd ? "AVX2" : "scalar", fails);
+    // legs: the hand-over (the default path; it needs AVX2), then the generic cavity walk with the batched AVX2 flip
+    // tests and with the scalar ones; each against a swap-loop instance fed in step with it.
+    for (int pass = simd ? 0 : 2; pass < 3; ++pass) {
+        for (size_t i = 0; i < cases.size(); ++i) fails += !check(cases[i], pass == 0 && (i < 6 || i + 1 == cases.size()), pass == 1, pass == 0);
+        printf("%zu cases (%s), %d failed so far\n", cases.size(),
+               pass == 0 ? "hand-over on" : pass == 1 ? "hand-over off, AVX2 flip tests" : "hand-over off, scalar flip tests", fails);
     }
     if (path) {
-        uint64_t ha = 0, hs = 0, hr = 0;
-        const double ta = time_inserts(file, false, simd, ha), ts = time_inserts(file, false, false, hs),
-                     tr = time_inserts(file, true, false, hr);
-        printf("%s inserts: cavity+%s %.2f ms, cavity+scalar %.2f ms, swap loop %.2f ms (x%.2f); facet-edge hash %016llx %s\n",
-               path, simd ? "AVX2" : "scalar", ta, ts, tr, tr / ta, (unsigned long long)ha,
-               ha == hr && hs == hr ? "equal" : "DIFFERENT");
-        if (ha != hr || hs != hr) fails++;
+        uint64_t hh = 0, ha = 0, hs = 0, hr = 0;
+        const double th = time_inserts(file, false, false, true, hh), ta = time_inserts(file, false, simd, false, ha),
+                     ts = time_inserts(file, false, false, false, hs), tr = time_inserts(file, true, false, false, hr);
+        printf("%s inserts: hand-over %.2f ms, cavity+%s %.2f ms, cavity+scalar %.2f ms, swap loop %.2f ms (x%.2f); facet-edge hash %016llx %s\n",
+               path, th, simd ? "AVX2" : "scalar", ta, ts, tr, tr / th, (unsigned long long)hh,
+               hh == hr && ha == hr && hs == hr ? "equal" : "DIFFERENT");
+        if (hh != hr || ha != hr || hs != hr) fails++;
     }
     return fails ? 1 : 0;
 }

@@ -28,12 +28,19 @@ int main(int argc, char **argv) {
     const float rw = (float)(std::abs(b[1] - b[0]) + 2.0), rh = (float)(std::abs(b[3] - b[2]) + 2.0);
     double best = 1e30, best_ticks_per_ms = 0;
     uint64_t hash = 0;
+    long n_cavity = 0, n_handover = 0, n_ho_bail = 0, n_loop = 0;
+#ifdef AOS_SD_HANDOVER   // (a variant built against an older subdiv2d.h has no hand-over)
+    const bool handover = !getenv("AOS_SD_NO_HANDOVER");   // (set: the generic cavity walk only)
+#endif
     aos::SdProf bestp{};
     for (int rep = 0; rep < reps; ++rep) {
 #ifdef AOS_SD_PROF
         aos::g_sdprof = aos::SdProf{};
 #endif
         aos::Subdiv2D sd;
+#ifdef AOS_SD_HANDOVER
+        sd.set_handover(handover);
+#endif
         sd.reserve(n);
         const auto t0 = std::chrono::steady_clock::now();
         const unsigned long long c0 = __rdtsc();
@@ -53,12 +60,17 @@ int main(int argc, char **argv) {
             bestp = aos::g_sdprof;
 #endif
         }
+        n_cavity = sd.n_cavity; n_loop = sd.n_loop;
+#ifdef AOS_SD_HANDOVER
+        n_handover = sd.n_handover; n_ho_bail = sd.n_ho_bail;
+#endif
         std::vector<float> e;
         sd.voronoi_edges(e);
         hash = 1469598103934665603ull;
         for (float v : e) { uint32_t u; memcpy(&u, &v, 4); hash = (hash ^ u) * 1099511628211ull; }
     }
-    printf("inserts %d: best %.2f ms of %d; facet-edge hash %016llx", n, best, reps, (unsigned long long)hash);
+    printf("inserts %d: best %.2f ms of %d; facet-edge hash %016llx; cavity %ld (hand-over %ld, bailed out %ld), swap loop %ld", n, best, reps,
+           (unsigned long long)hash, n_cavity, n_handover, n_ho_bail, n_loop);
 #ifdef AOS_SD_PROF
     const double k = 1.0 / best_ticks_per_ms;   // ticks -> ms
     printf(" | locate %.2f ms (%.2f steps/insert), dfs %.2f ms (%.2f steps/insert), write %.2f ms, rest %.2f ms",
