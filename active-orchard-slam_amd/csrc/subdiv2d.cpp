@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <climits>
 #include <cmath>
 #include <cstddef>
 #include <cstring>
@@ -24,6 +25,10 @@ namespace aos { SdProf g_sdprof; }
 #endif
 
 namespace aos {
+
+#ifdef AOS_SD_POISON
+long sd_poison_reads = 0;
+#endif
 
 namespace {
 // triangleArea (double from float coordinates)
@@ -132,6 +137,8 @@ void Subdiv2D::init_delaunay(float rx, float ry, float rw, float rh, int rect_mo
     vp.clear(); vd.clear(); vfirst.clear(); vtype.clear(); rec.clear();
     recent = 0;
     ho_valid = false;
+    pending = false;   // a pending star of the previous point set is dropped with its records
+    loc_k = -1;
     tlx = rx; tly = ry; brx = rx + rw; bry = ry + rh;
     vp.push_back(V2f{0.f, 0.f}); vd.push_back(V2d{0.0, 0.0, 0.0, 0, 0}); vfirst.push_back(0); vtype.push_back(-1);
     rec.push_back(Rec{});                                                      // quad-edge 0 (NULL)
@@ -148,6 +155,11 @@ int Subdiv2D::locate(float px, float py, int &out_edge, int &out_vertex) {
     int vertex = 0;
     const int max_edges = (int)rec.size() * 4;
     if (px < tlx || py < tly || px >= brx || py >= bry) return -1;
+    loc_k = -1;
+    if (pending) {
+        if (locate_star(px, py, out_edge)) { out_vertex = 0; return 0; }
+        flush();   // the walk below starts again from the same recentEdge
+    }
     SDP_T0(t_loc);
     // The walk carries the current edge's end points o = Org(edge), d = Dst(edge): Onext(edge) keeps the origin and
     // Dprev(edge) the destination, and both end at the left face's third vertex a (Dst Onext = Org Dprev), so a step
@@ -222,6 +234,7 @@ bool Subdiv2D::insert(float x, float y) {
         return true;
     }
     ++n_loop;
+    flush();
     ho_valid = false;   // the swap loop leaves no ring arrays behind
     int base = new_edge();
     const int first_point = org(curr_edge);
@@ -515,6 +528,7 @@ __attribute__((noinline)) int Subdiv2D::ho_walk(int e, const V2d &Pin, int sA, R
     int *top = stk;
     RingP n = ring_ptrs(N);
     int cap = N.cap;
+    const int hz = ho_hz;
     for (;;) {
         SDP_INC(dfs_steps);
         const int t = oprev(e), w = dst(t), o = org(e);
@@ -527,6 +541,8 @@ __attribute__((noinline)) int Subdiv2D::ho_walk(int e, const V2d &Pin, int sA, R
         if ((aTDO > 0) & (val < -(FLT_EPSILON * 0.125))) {
             V2d &W = vd[w];
             if (W.stamp == sA) return -1;
+            // a ring vertex of the pending star outside the cavity: the child edges may be Sym L_i (subdiv2d.h)
+            if (W.stamp == hz) { ho_pocket = true; return -1; }
             W.stamp = sA;
             W.spoke = e;                                       // e becomes w -> p
             last_flip = e;
@@ -649,6 +665,7 @@ AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, i
                 j = jm;
             }
             // the leaf S_j (apex x_j-1), then the stacked links L_j+1 .. L_k-1
+            ho_jD = j;
             HO_ROOM(1);
             n.bd[q] = o.sp[j]; n.bu[q] = o.bu[j]; n.ba[q] = o.bu[j - 1]; n.sp[q] = V[o.bu[j]].spoke;
             n.x[q] = o.x[j]; n.y[q] = o.y[j]; n.n[q] = o.n[j]; n.ax[q] = o.x[j - 1]; n.ay[q] = o.y[j - 1]; n.an[q] = o.n[j - 1];
@@ -718,6 +735,7 @@ AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, i
                 j = jn;
             }
             // the leaf Sym S_j (apex x_j+1)
+            ho_jA = j;
             HO_ROOM(1);
             n.bd[q] = o.sp[j] ^ 2; n.bu[q] = c; n.ba[q] = o.bu[j + 1]; n.sp[q] = Cv.spoke;
             n.x[q] = Cv.x; n.y[q] = Cv.y; n.n[q] = Cv.n2; n.ax[q] = o.x[j + 1]; n.ay[q] = o.y[j + 1]; n.an[q] = o.n[j + 1];
@@ -735,16 +753,44 @@ AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, i
     return true;
 }
 
+AOS_AVX2 static int find_int(const int *a, int m, int v) {   // the first i < m with a[i] == v, or -1
+    const __m256i V = _mm256_set1_epi32(v);
+    int i = 0;
+    for (; i + 8 <= m; i += 8) {
+        const int mask = _mm256_movemask_ps(_mm256_castsi256_ps(_mm256_cmpeq_epi32(_mm256_loadu_si256((const __m256i *)(a + i)), V)));
+        if (mask) return i + __builtin_ctz(mask);
+    }
+    for (; i < m; ++i) if (a[i] == v) return i;
+    return -1;
+}
+
 // insert_cavity with the hand-over: the same walk, started either through the previous star's arrays (ho_fast) or,
 // when p does not lie in a fan triangle of the previous insert, from the three roots by ho_walk; both leave the new
 // star's ring in the other buffer.
 bool Subdiv2D::insert_cavity_ho(int e0, int p) {
-    if (++stamp >= (1 << 29)) { for (V2d &x : vd) x.stamp = 0; stamp = 1; }
+    if (++stamp >= (1 << 29)) {
+        flush();   // (the pocket test needs the pending ring's stamps)
+        for (V2d &x : vd) x.stamp = 0;
+        stamp = 1; ho_stamp = -1;
+    }
     const int sA = 2 * stamp;
-    const int eB = lnext(e0), eA = lnext(eB);          // root link edges in walk order: eA, eB, e0
-    if (lnext(eA) != e0) return false;
-    const int first = org(e0), v1 = org(eB), v2 = org(eA);
-    if (first == v1 || v1 == v2 || v2 == first) return false;
+    Ring &O = ho[ho_cur], &N = ho[ho_cur ^ 1];
+    int eA = 0, eB = 0, first, v1, v2;
+    int shift = -1, k = -1;
+    if (loc_k >= 0) {
+        // located on the ring arrays (locate_star): slot, rotation and corners without a record read
+        const RingP o = ring_ptrs(O);
+        k = loc_k; shift = loc_shift;
+        const int xk = o.bu[k], xk1 = o.bu[k - 1], c = ho_c;
+        if (shift == 0) { first = xk; v1 = xk1; v2 = c; }         // e0 = L_k
+        else if (shift == 2) { first = xk1; v1 = c; v2 = xk; }    // e0 = S_k-1
+        else { first = c; v1 = xk; v2 = xk1; }                    // e0 = Sym S_k
+    } else {
+        eB = lnext(e0); eA = lnext(eB);                // root link edges in walk order: eA, eB, e0
+        if (lnext(eA) != e0) return false;
+        first = org(e0); v1 = org(eB); v2 = org(eA);
+    }
+    if (first == v1 || v1 == v2 || v2 == first) { flush(); return false; }
     const size_t cap = vp.size() + 8;
     if (dfs_stack.size() < cap) dfs_stack.resize(2 * cap);
     // the quad-edges the three new_edge() calls below will hand out, so that the roots' spokes are known to the walk
@@ -760,30 +806,38 @@ bool Subdiv2D::insert_cavity_ho(int e0, int p) {
     F.stamp = A.stamp = B.stamp = sA;
     F.spoke = cn[0]; A.spoke = cn[1]; B.spoke = cn[2];           // first -> p, v1 -> p, v2 -> p
     const V2d P = vd[p];
-    Ring &O = ho[ho_cur], &N = ho[ho_cur ^ 1];
     ring_reserve(N, 8);
     int q = 0, lf = -1;
     SDP_T0(t_dfs);
-    // the guard: a corner is the previous centre, and the opposite root is the link edge of the slot it carries
-    int shift = -1, L = 0, asc = 0, desc = 0;
-    if (ho_valid) {
+    bool fast = loc_k >= 0;
+    if (!fast && ho_valid) {
+        // the guard: a corner is the previous centre, and the opposite root is the link edge of the slot it carries
+        // (the star is not pending here: the generic locate has flushed it)
+        int L = 0, asc = 0, desc = 0;
         const int c = ho_c;
         if (v2 == c) { shift = 0; asc = eA; desc = eB; L = e0; }
         else if (v1 == c) { shift = 2; L = eA; asc = eB; desc = e0; }
         else if (first == c) { shift = 1; desc = eA; L = eB; asc = e0; }
-    }
-    bool fast = false;
-    if (shift >= 0) {
-        const int k = ri()[2 * (ptrdiff_t)L + 3];
-        const RingP o = ring_ptrs(O);
-        if ((unsigned)k < (unsigned)O.m && o.bd[k] == L && (o.sp[k] ^ 2) == asc && o.sp[k - 1] == desc) {
-            fast = true;
-            last_ho_slot = k; last_ho_ring = O.m;
-            if (!ho_fast(O, N, k, shift, p, ho_c, sA, q)) { ++n_ho_bail; ho_valid = false; last_ho_slot = -1; return false; }
-            lf = ho_lf;
+        if (shift >= 0) {
+            k = chk(ri()[2 * (ptrdiff_t)L + 3]);
+            const RingP o = ring_ptrs(O);
+            fast = (unsigned)k < (unsigned)O.m && o.bd[k] == L && (o.sp[k] ^ 2) == asc && o.sp[k - 1] == desc;
         }
     }
-    if (!fast) {
+    if (fast) {
+        last_ho_slot = k; last_ho_ring = O.m;
+        ho_hz = pending ? ho_stamp : -1;
+        ho_pocket = false;
+        if (!ho_fast(O, N, k, shift, p, ho_c, sA, q)) {
+            if (ho_pocket) ++n_ho_pocket; else ++n_ho_bail;
+            flush();   // (ho_fast has changed no record: the pending ring is still the whole truth)
+            ho_valid = false; last_ho_slot = -1;
+            return false;
+        }
+        lf = ho_lf;
+    } else {
+        flush();
+        ho_hz = -1;
         if ((q = ho_walk(eA, P, sA, N, 0, -1)) < 0 || (q = ho_walk(eB, P, sA, N, q, ho_lf)) < 0 ||
             (q = ho_walk(e0, P, sA, N, q, ho_lf)) < 0) {
             ho_valid = false;
@@ -802,17 +856,171 @@ bool Subdiv2D::insert_cavity_ho(int e0, int p) {
     const int c0 = new_edge(), c1 = new_edge(), c2 = new_edge();   // first -> p, v1 -> p, v2 -> p (= cn[0 .. 2])
     (void)c0; (void)c1;
     vfirst[p] = sym(lf >= 0 ? lf : c2);   // the last setEdgePoints with p as destination
-    ring_pass_ho(ri(), vfirst.data(), n.bd, n.bu, n.sp, m, p);
-    ho_cur ^= 1; ho_c = p; ho_valid = true;
+    if (pending) retire(O, ho_jA, ho_jD);   // (fast: what survives of the old star; the rest is N's to write)
+    ho_cur ^= 1; ho_c = p; ho_valid = true; ho_stamp = sA;
     n_handover += fast;
+    pending = false;
+    if (use_def) {
+        // recentEdge = e0 in the new ring: the last leaf if its test did not swap, else the spoke of its apex
+        int s = m - 1, kind = 0;
+        if (n.bd[s] != e0) { kind = 2; s = find_int(n.sp, m, e0); }
+        if (s >= 0) {
+            pending = true; rs_kind = kind; rs_slot = s;
+            ++n_deferred;
+#ifdef AOS_SD_POISON
+            for_pending([](int &f) { f = INT_MIN; });
+#endif
+        }
+    }
+    if (!pending) ring_pass_ho(ri(), vfirst.data(), n.bd, n.bu, n.sp, m, p);
     SDP_ADD(t_write, t_wr);
     return true;
 }
+
+// The ring pass on the pending star.
+void Subdiv2D::flush() {
+    if (!pending) return;
+    SDP_T0(t_wr);
+    Ring &R = ho[ho_cur];
+    const RingP r = ring_ptrs(R);
+    ring_pass_ho(ri(), vfirst.data(), r.bd, r.bu, r.sp, R.m, ho_c);
+    pending = false;
+    SDP_ADD(t_write, t_wr);
+}
+
+// The pending ring O after the next insert has been walked through it: slots jA .. jD (cyclic) kept their spokes. The
+// pass restricted to them writes a superset of what the new ring's pass will not write again: of these slots' fields
+// only Onext(L_jA), Oprev(Sym L_jD+1) (both links were tested: leaves or spokes of the new ring), Onext / Oprev of
+// S_jD and Sym S_jA (link edges of the new ring now) and firstEdge of x_jA, x_jD (new ring vertices) are rewritten.
+void Subdiv2D::retire(Ring &O, int jA, int jD) {
+    const RingP o = ring_ptrs(O);
+    int *const R = ri();
+    const int m = O.m, c = ho_c;
+#ifdef AOS_SD_PROF
+    g_sdprof.ring_slots += m;
+    g_sdprof.kept_slots += (jD - jA + m) % m + 1;
+#endif
+    for (int j = jA;; j = j + 1 == m ? 0 : j + 1) {
+        const int L = o.bd[j], sLn = o.bd[j + 1] ^ 2, S = o.sp[j], sS = S ^ 2;
+        R[2 * (ptrdiff_t)L] = S;
+        R[2 * (ptrdiff_t)L + 3] = j;
+        R[2 * (ptrdiff_t)sLn + 1] = S;
+        int *a = R + 2 * (ptrdiff_t)S, *b = R + 2 * (ptrdiff_t)sS;
+        a[0] = sLn; a[1] = L; a[2] = o.bu[j];
+        b[0] = o.sp[j - 1] ^ 2; b[1] = o.sp[j + 1] ^ 2; b[2] = c;
+        vfirst[o.bu[j]] = S;
+        if (j == jD) break;
+    }
+}
+
+template <class Fn> void Subdiv2D::for_pending(Fn f) {
+    Ring &Rg = ho[ho_cur];
+    const RingP r = ring_ptrs(Rg);
+    int *const R = ri();
+    for (int k = 0; k < Rg.m; ++k) {
+        const int L = r.bd[k], sLn = r.bd[k + 1] ^ 2, S = r.sp[k], sS = S ^ 2;
+        f(R[2 * (ptrdiff_t)L]); f(R[2 * (ptrdiff_t)L + 3]); f(R[2 * (ptrdiff_t)sLn + 1]);
+        for (int i = 0; i < 3; ++i) { f(R[2 * (ptrdiff_t)S + i]); f(R[2 * (ptrdiff_t)sS + i]); }
+        f(vfirst[r.bu[k]]);
+    }
+}
+
+// locate()'s loop while it stays inside the pending star of c = ho_c (subdiv2d.h): the current edge is (kind, slot) of
+// the ring, its end points and the left face's third vertex come from the ring arrays and c. The predicates are
+// locate()'s (same operands, same order); with every sign non-zero its branches reduce to: both right -> found;
+// right of Onext only -> Dprev; else Onext. Returns false, having changed nothing, where the generic walk has to run.
+bool Subdiv2D::locate_star(float px, float py, int &out_edge) {
+    SDP_T0(t_loc);
+    Ring &Rg = ho[ho_cur];
+    const RingP r = ring_ptrs(Rg);
+    const int m = Rg.m;
+    const V2d C = vd[ho_c];
+    const double x = px, y = py;
+    auto rof = [&](double ox, double oy, double dx, double dy) {
+        const double cw = (dx - x) * (oy - y) - (dy - y) * (ox - x);
+        return (cw > 0) - (cw < 0);
+    };
+    int kind = rs_kind, s = rs_slot;
+    SDP_INC(star_loc);
+    double ox = r.x[s], oy = r.y[s], dx, dy;
+    if (kind == 0) { dx = r.x[s - 1]; dy = r.y[s - 1]; } else { dx = C.x; dy = C.y; }
+    const int roc = rof(ox, oy, dx, dy);
+    bool found = false;
+    if (roc < 0 || (roc > 0 && kind == 2)) {   // (zero: generic; right of a link edge: Sym L leaves the star)
+        if (roc > 0) { kind = 3; std::swap(ox, dx); std::swap(oy, dy); }
+        for (int it = 0; it < 2 * m + 8; ++it) {
+            SDP_INC(loc_iters);
+            SDP_INC(star_steps);
+            double ax, ay;
+            if (kind == 0) { ax = C.x; ay = C.y; }
+            else if (kind == 2) { ax = r.x[s + 1]; ay = r.y[s + 1]; }
+            else { ax = r.x[s - 1]; ay = r.y[s - 1]; }
+            const int ron = rof(ox, oy, ax, ay);   // Onext: o -> a
+            const int rod = rof(ax, ay, dx, dy);   // Dprev: a -> d
+            if (ron == 0 || rod == 0) break;
+            if (ron > 0 && rod > 0) { found = true; break; }
+            if (ron > 0) {   // Dprev
+                if (kind == 3) break;                                       // Sym L_s
+                if (kind == 0) { kind = 3; s = s ? s - 1 : m - 1; }         // L_s -> Sym S_s-1
+                else s = s + 1 == m ? 0 : s + 1;                            // S_s -> S_s+1
+                ox = ax; oy = ay;
+            } else {         // Onext
+                if (kind == 2) break;                                       // Sym L_s+1
+                if (kind == 0) kind = 2;                                    // L_s -> S_s
+                else s = s ? s - 1 : m - 1;                                 // Sym S_s -> Sym S_s-1
+                dx = ax; dy = ay;
+            }
+        }
+    }
+    if (found) {
+        const float fox = (float)ox, foy = (float)oy, fdx = (float)dx, fdy = (float)dy;   // (exact: they were floats)
+        double t1 = std::fabs(px - fox); t1 += std::fabs(py - foy);
+        double t2 = std::fabs(px - fdx); t2 += std::fabs(py - fdy);
+        double t3 = std::fabs(fox - fdx); t3 += std::fabs(foy - fdy);
+        if (t1 < FLT_EPSILON || t2 < FLT_EPSILON ||
+            ((t1 < t3 || t2 < t3) && std::fabs(tri_area(px, py, fox, foy, fdx, fdy)) < FLT_EPSILON))
+            found = false;   // a vertex or on an edge
+    }
+    if (found) {
+        // the left face of L_s and of Sym S_s is fan triangle s, that of S_s is triangle s + 1
+        if (kind == 0) { recent = r.bd[s]; loc_k = s; loc_shift = 0; }
+        else if (kind == 2) { recent = r.sp[s]; loc_k = s + 1 == m ? 0 : s + 1; loc_shift = 2; }
+        else { recent = r.sp[s] ^ 2; loc_k = s; loc_shift = 1; }
+        out_edge = recent;
+        SDP_INC(star_found);
+    }
+    SDP_ADD(t_locate, t_loc);
+    return found;
+}
 #else
 bool Subdiv2D::insert_cavity_ho(int e0, int p) { return insert_cavity<false>(e0, p); }
+void Subdiv2D::flush() {}
+bool Subdiv2D::locate_star(float, float, int &) { return false; }
+template <class Fn> void Subdiv2D::for_pending(Fn) {}
 #endif
 
+// Compared through a flushed view: a pending star's fields are saved, the pass is run, and after the comparison the
+// fields are put back, so that the live instance stays exactly as deferred as it was.
 bool Subdiv2D::same_state(const Subdiv2D &o) const {
+    Subdiv2D *const both[2] = {const_cast<Subdiv2D *>(this), const_cast<Subdiv2D *>(&o)};
+    std::vector<int> saved[2];
+    for (int i = 0; i < 2; ++i) {
+        Subdiv2D &t = *both[i];
+        if (!t.pending || (i == 1 && both[1] == both[0])) continue;
+        t.for_pending([&](int &f) { saved[i].push_back(f); });
+        t.flush();
+        t.pending = true;
+    }
+    const bool eq = same_records(o);
+    for (int i = 1; i >= 0; --i) {
+        if (saved[i].empty()) continue;
+        size_t at = 0;
+        both[i]->for_pending([&](int &f) { f = saved[i][at++]; });
+    }
+    return eq;
+}
+
+bool Subdiv2D::same_records(const Subdiv2D &o) const {
     if (rec.size() != o.rec.size() || vp.size() != o.vp.size() || recent != o.recent || free_q != o.free_q ||
         free_p != o.free_p)
         return false;
@@ -830,6 +1038,7 @@ bool Subdiv2D::same_state(const Subdiv2D &o) const {
 // straight from the rings; Onext(Rot e) = Rot^-1 Oprev(e) gives the dual ones. pt[0] / pt[2] are
 // the primal end points; the dual pt[1] / pt[3] (Voronoi vertices) start unset (calcVoronoi).
 Subdiv2D::Raw Subdiv2D::raw() {
+    flush();
     const int n = (int)rec.size();
     qx.assign(8 * (size_t)n, 0);
     auto rot3 = [](int x) { return (x & ~3) + ((x + 3) & 3); };
@@ -875,6 +1084,7 @@ AOS_AVX2 static void export_recs_avx2(const int *R, int *out, int q0, int q1) {
 }
 
 Subdiv2D::Raw Subdiv2D::raw_into(void *dst, int chunk_recs, const std::function<void(size_t, size_t)> &written) const {
+    const_cast<Subdiv2D *>(this)->flush();   // (pending state is not observable: the export sees the written star)
     const int n = (int)rec.size(), nv = (int)vp.size();
     int *qe = static_cast<int *>(dst);
     static const bool avx2 = simd_ok();
@@ -902,6 +1112,7 @@ int Subdiv2D::facet_next(int e) const {   // getEdge(e, NEXT_AROUND_LEFT = 0x13)
 }
 
 void Subdiv2D::calc_voronoi() {
+    flush();
     raw();
     const int total = (int)rec.size();
     auto next = [&](int e) { return qx[8 * (size_t)(e >> 2) + (e & 3)]; };
@@ -941,6 +1152,7 @@ void Subdiv2D::calc_voronoi() {
 // rotateEdge(firstEdge, 1) and walking NEXT_AROUND_LEFT; vtx[edgeOrg(t)] (index 0 = the (0,0)
 // NULL vertex when a circumcentre was not created).
 void Subdiv2D::voronoi_facets(std::vector<int> &off, std::vector<float> &xy) {
+    flush();
     calc_voronoi();
     off.assign(1, 0);
     xy.clear();

@@ -43,6 +43,26 @@
 // oprev / dst / vertex loads, and the new ring is copied from the old one in runs. A spoke's ring links (ring_pass):
 //   Oprev(S_j) = L_j,  Oprev(Sym S_j) = Sym S_j+1,  Sym Onext(Sym S_j) = S_j-1,  Sym Onext(S_j) = L_j+1.
 // A link edge that swaps leaves the star: the generic walk runs from it. All of this state is per instance.
+//
+// Deferred star (set_deferred, on by default with the hand-over). The next insert's pass rewrites about nine tenths of
+// what ring_pass writes (on seed rows a ring of 60 slots keeps 4-5 of its spokes), and between two inserts only
+// locate() reads records, nearly always inside that star. So a hand-over insert does not run its ring pass: the star
+// stays *pending*, described by the ring arrays alone. Pending are exactly the fields ring_pass writes: per slot k
+// Onext(L_k), Oprev(Sym L_k+1), the slot int of L_k, every field of S_k and Sym S_k, and firstEdge of x_k. All that
+// faces outward from the ring (Oprev(L_k), Onext(Sym L_k), the link edges' end points) is valid in the records.
+//   * locate() walks its loop on the arrays while it stays in the star (locate_star: same predicate arithmetic and
+//     branch order; transitions Onext L_s = S_s, Dprev L_s = Sym S_s-1, Dprev S_s = S_s+1, Onext Sym S_s = Sym S_s-1;
+//     Onext S_s and Dprev Sym S_s are Sym L, which leaves the star). Any zero predicate, a step out of the star, or a
+//     vertex / on-edge result flushes and restarts the generic walk from the same recentEdge.
+//   * The next hand-over insert reads the pending ring O, builds N, and retires O: the spokes between the ends of the
+//     ascending and descending chains (slots jA .. jD) did not flip, and the ring pass restricted to those slots writes
+//     every field of O's pass that N's pass will not write again. N stays pending.
+//   * The generic walk from a swapped link L_j reads only outward fields, unless a swap's apex is a ring vertex of O
+//     that is not in the cavity yet (a pocket of a non-convex star): its child edge can be Sym L_i, whose Oprev is
+//     pending. Ring vertices carry O's stamp, so the swap sees it for free: flush, swap loop (n_ho_pocket).
+//   * flush() runs the pass on the pending ring. Everything that reads records generically calls it first.
+// -DAOS_SD_POISON (checkers only) stores INT_MIN in every field as it becomes pending and counts record reads that
+// return it (sd_poison_reads): a stale read fails deterministically.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -50,12 +70,21 @@
 #include <vector>
 
 #define AOS_SD_HANDOVER 1   // set_handover(), n_handover and n_ho_bail exist (tools/sdcheck/sdprof.cpp)
+#define AOS_SD_DEFERRED 1   // set_deferred(), flush(), n_deferred and n_ho_pocket exist
 
 namespace aos {
 
 // per-phase counters of a build with -DAOS_SD_PROF (tools/sdcheck/sdprof.cpp); TSC ticks
-struct SdProf { unsigned long long t_locate = 0, t_dfs = 0, t_write = 0, loc_iters = 0, dfs_steps = 0; };
+struct SdProf {
+    unsigned long long t_locate = 0, t_dfs = 0, t_write = 0, loc_iters = 0, dfs_steps = 0;
+    // deferred star: locates started on the ring arrays, those that ended there, their steps; slots of the rings that
+    // were retired and how many of them kept their spoke
+    unsigned long long star_loc = 0, star_found = 0, star_steps = 0, ring_slots = 0, kept_slots = 0;
+};
 extern SdProf g_sdprof;
+#ifdef AOS_SD_POISON
+extern long sd_poison_reads;   // record reads that returned a pending field's poison (must stay 0)
+#endif
 
 class Subdiv2D {
   public:
@@ -65,10 +94,14 @@ class Subdiv2D {
     // Subdiv2D::insert; returns false where OpenCV throws (the reference catches and skips).
     bool insert(float x, float y);
     // 0: cavity DFS + bulk write (default); 1: always OpenCV's swap loop (reference / cross-check)
-    void set_swap_loop(bool on) { force_loop = on; }
-    void set_simd(bool on) { use_avx2 = on && simd_ok(); }   // batched boundary flip tests on AVX2 (off by default)
+    void set_swap_loop(bool on) { flush(); force_loop = on; }
+    void set_simd(bool on) { flush(); use_avx2 = on && simd_ok(); }   // batched boundary flip tests on AVX2 (off by default)
     // walk the previous insert's star through the arrays it left (see above); needs AVX2, else the generic walk runs
-    void set_handover(bool on) { use_ho = on && simd_ok(); ho_valid = false; }
+    void set_handover(bool on) { flush(); use_ho = on && simd_ok(); ho_valid = false; }
+    // leave a hand-over insert's star pending in the ring arrays (see above); off: every insert runs its ring pass
+    void set_deferred(bool on) { flush(); use_def = on; }
+    void flush();                    // writes a pending star into the records (no-op without one)
+    bool star_pending() const { return pending; }
     static bool simd_ok() {
 #if defined(__x86_64__)
         return __builtin_cpu_supports("avx2");
@@ -81,6 +114,8 @@ class Subdiv2D {
     long n_cavity = 0, n_loop = 0;   // inserts done by each path
     long n_handover = 0;             // cavity inserts that walked the previous star's arrays (part of n_cavity)
     long n_ho_bail = 0;              // hand-over walks that met a cavity vertex twice: redone by the swap loop
+    long n_deferred = 0;             // inserts that left their star pending (part of n_cavity)
+    long n_ho_pocket = 0;            // hand-over walks whose swap had a ring vertex of the pending star as apex: flushed, swap loop
     int last_ho_slot = -1, last_ho_ring = 0;   // the last insert's fan-triangle slot and ring length (-1: no hand-over)
     // getVoronoiFacetList(idx = {}): per real vertex (in vertex order) the facet polygon.
     // Emits the reference's edge list directly: (p_i, p_{i+1 mod n}) for facets with >= 2 points
@@ -134,6 +169,12 @@ class Subdiv2D {
     Ring ho[2];
     int ho_cur = 0, ho_c = 0, ho_lf = -1;
     bool ho_valid = false, use_ho = simd_ok();
+    // deferred star: ho[ho_cur] is pending; recentEdge as (kind, slot) of that ring; the fan triangle locate_star found
+    bool pending = false, use_def = true, ho_pocket = false;
+    int rs_kind = 0, rs_slot = 0;    // kind: 0 L_s, 2 S_s, 3 Sym S_s
+    int loc_k = -1, loc_shift = 0;   // set by locate_star (loc_k < 0: the generic locate ran)
+    int ho_stamp = -1, ho_hz = -1;   // the pending ring's vertex stamp; the stamp ho_walk treats as a pocket (-1: none)
+    int ho_jA = 0, ho_jD = 0;        // ho_fast: the slots where the ascending and descending chains ended
     float tlx = 0, tly = 0, brx = 0, bry = 0;
 
     static int sym(int e) { return e ^ 2; }
@@ -143,10 +184,15 @@ class Subdiv2D {
     int &on(int e) { return ri()[2 * (ptrdiff_t)e]; }
     int &op(int e) { return ri()[2 * (ptrdiff_t)e + 1]; }
     int &orgr(int e) { return ri()[2 * (ptrdiff_t)e + 2]; }
-    int onext(int e) const { return ri()[2 * (ptrdiff_t)e]; }
-    int oprev(int e) const { return ri()[2 * (ptrdiff_t)e + 1]; }
-    int org(int e) const { return ri()[2 * (ptrdiff_t)e + 2]; }
-    int dst(int e) const { return ri()[2 * (ptrdiff_t)(e ^ 2) + 2]; }
+#ifdef AOS_SD_POISON
+    static int chk(int v) { sd_poison_reads += v == INT32_MIN; return v; }
+#else
+    static int chk(int v) { return v; }
+#endif
+    int onext(int e) const { return chk(ri()[2 * (ptrdiff_t)e]); }
+    int oprev(int e) const { return chk(ri()[2 * (ptrdiff_t)e + 1]); }
+    int org(int e) const { return chk(ri()[2 * (ptrdiff_t)e + 2]); }
+    int dst(int e) const { return chk(ri()[2 * (ptrdiff_t)(e ^ 2) + 2]); }
     int lnext(int e) const { return oprev(sym(e)); }          // NEXT_AROUND_LEFT
     int dprev(int e) const { return sym(oprev(sym(e))); }     // PREV_AROUND_DST
     int lprev(int e) const { return sym(onext(e)); }          // PREV_AROUND_LEFT
@@ -154,7 +200,7 @@ class Subdiv2D {
     int new_edge();
     int new_point(float x, float y, int type);
     void splice(int a, int b) {
-        const int an = on(a), bn = on(b);
+        const int an = chk(on(a)), bn = chk(on(b));
         on(a) = bn; on(b) = an;
         op(bn) = a; op(an) = b;
     }
@@ -163,6 +209,10 @@ class Subdiv2D {
     void swap_edge(int e);
     void delete_edge(int e);
     int locate(float px, float py, int &edge, int &vertex);
+    bool locate_star(float px, float py, int &edge);
+    void retire(Ring &O, int jA, int jD);
+    template <class F> void for_pending(F f);   // f(int &field) over every pending field of ho[ho_cur]
+    bool same_records(const Subdiv2D &o) const;
     void swap_loop(int curr_edge, int first_point, int curr_point);
     void flip_tests_scalar(const int *es, int n, const V2d &P, int *out) const;
     void flip_tests_avx2(const int *es, int n, const V2d &P, int *out) const;

@@ -69,6 +69,23 @@ def frame_from_trace(d):
     nc_med = sorted(p[1] - p[2] for p in per)[len(per) // 2]
     print(f"trace frames ({len(per)}): median {n_med} launches, {t_med:.1f} us kernel time, {nc_med:.1f} us without "
           f"copies and host stores (min / max launches {per[0][0]} / {per[-1][0]})")
+    # the frame's longest stretch with no kernel running (on the sequential loop: the host Subdiv2D replay, between the
+    # seed merge and the facet builder) and the kernels on either side of it
+    gaps = []
+    for a, b in zip(starts, starts[1:]):
+        end, after = int(rows[a]["End_Timestamp"]), rows[a]["Kernel_Name"]
+        best = (0, "", "")
+        for r in rows[a + 1:b]:
+            g = int(r["Start_Timestamp"]) - end
+            if g > best[0]:
+                best = (g, after, r["Kernel_Name"])
+            if int(r["End_Timestamp"]) > end:
+                end, after = int(r["End_Timestamp"]), r["Kernel_Name"]
+        gaps.append(best)
+    gaps.sort()
+    g = gaps[len(gaps) // 2]
+    print(f"longest kernel-free gap per frame: median {g[0] / 1e3:.1f} us (min {gaps[0][0] / 1e3:.1f}, max {gaps[-1][0] / 1e3:.1f}), "
+          f"after {g[1][:40]} before {g[2][:40]}")
 
 
 if __name__ == "__main__":

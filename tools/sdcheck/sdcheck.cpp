@@ -1,6 +1,10 @@
 // Equivalence checker for aos::Subdiv2D's cavity insert (subdiv2d.h): the same seeds go into two
 // instances, one forced onto OpenCV's swap loop, and the complete internal state (rings, end points,
 // firstEdge, recentEdge, free lists) must be equal after every insert. Also times both paths.
+// The deferred leg (a hand-over insert's star stays pending in arrays, subdiv2d.h) runs twice: compared after every
+// insert (same_state looks through a flushed view and leaves the star pending), and compared only after the last
+// insert, so that pending stars follow each other with no call in between. Built with -DAOS_SD_POISON, every pending
+// field holds INT_MIN and a record read that returns it fails the case.
 // usage: sdcheck [seeds.bin]   (seeds.bin: int n, n double pairs, 4 double bounds)
 #include "subdiv2d.h"
 
@@ -24,12 +28,13 @@ static double uni() { return (splitmix() >> 11) * (1.0 / 9007199254740992.0); }
 
 struct Case { const char *name; std::vector<double> s; double b[4]; };
 
-static bool check(const Case &c, bool verbose, bool simd, bool handover) {
+static bool check(const Case &c, bool verbose, bool simd, bool handover, bool deferred, bool every) {
     float rx = (float)(c.b[0] - 1.0), ry = (float)(c.b[2] - 1.0);
     float rw = (float)(std::abs(c.b[1] - c.b[0]) + 2.0), rh = (float)(std::abs(c.b[3] - c.b[2]) + 2.0);
     aos::Subdiv2D a, r;
     a.set_simd(simd);
     a.set_handover(handover);
+    a.set_deferred(deferred);
     r.set_swap_loop(true);
     const int n = (int)c.s.size() / 2;
     a.reserve(n); r.reserve(n);
@@ -38,24 +43,32 @@ static bool check(const Case &c, bool verbose, bool simd, bool handover) {
         float x = (float)c.s[2 * i], y = (float)c.s[2 * i + 1];
         x = std::max(rx + 0.1f, std::min(rx + rw - 0.1f, x)); y = std::max(ry + 0.1f, std::min(ry + rh - 0.1f, y));
         const bool ka = a.insert(x, y), kr = r.insert(x, y);
-        if (ka != kr || !a.same_state(r)) {
+        if (ka != kr || ((every || i + 1 == n) && !a.same_state(r))) {
             printf("FAIL %s: state differs after insert %d of %d (%.9g, %.9g)\n", c.name, i, n, x, y);
             return false;
         }
     }
+    if (!deferred && a.n_deferred) { printf("FAIL %s: %ld stars deferred with the switch off\n", c.name, a.n_deferred); return false; }
     std::vector<float> ea, er;
     a.voronoi_edges(ea); r.voronoi_edges(er);
     if (ea.size() != er.size() || memcmp(ea.data(), er.data(), ea.size() * 4)) {
         printf("FAIL %s: facet edges differ\n", c.name);
         return false;
     }
+#ifdef AOS_SD_POISON
+    if (aos::sd_poison_reads) {
+        printf("FAIL %s: %ld record reads returned a pending field\n", c.name, aos::sd_poison_reads);
+        aos::sd_poison_reads = 0;
+        return false;
+    }
+#endif
     if (verbose)
-        printf("ok   %-22s n=%-7d cavity inserts %ld (hand-over %ld, bailed out %ld), swap-loop inserts %ld\n", c.name, n, a.n_cavity,
-               a.n_handover, a.n_ho_bail, a.n_loop);
+        printf("ok   %-22s n=%-7d cavity inserts %ld (hand-over %ld, deferred %ld, bailed out %ld, pockets %ld), swap-loop inserts %ld\n",
+               c.name, n, a.n_cavity, a.n_handover, a.n_deferred, a.n_ho_bail, a.n_ho_pocket, a.n_loop);
     return true;
 }
 
-static double time_inserts(const Case &c, bool loop, bool simd, bool handover, uint64_t &hash) {
+static double time_inserts(const Case &c, bool loop, bool simd, bool handover, bool deferred, uint64_t &hash) {
     float rx = (float)(c.b[0] - 1.0), ry = (float)(c.b[2] - 1.0);
     float rw = (float)(std::abs(c.b[1] - c.b[0]) + 2.0), rh = (float)(std::abs(c.b[3] - c.b[2]) + 2.0);
     const int n = (int)c.s.size() / 2;
@@ -65,6 +78,7 @@ static double time_inserts(const Case &c, bool loop, bool simd, bool handover, u
         sd.set_swap_loop(loop);
         sd.set_simd(simd);
         sd.set_handover(handover);
+        sd.set_deferred(deferred);
         sd.reserve(n);
         auto t0 = std::chrono::steady_clock::now();
         sd.init_delaunay(rx, ry, rw, rh, 0);
@@ -141,21 +155,27 @@ int main(int argc, char **argv) {
     }
     int fails = 0;
     const bool simd = aos::Subdiv2D::simd_ok();
-    // legs: the hand-over (the default path; it needs AVX2), then the generic cavity walk with the batched AVX2 flip
-    // tests and with the scalar ones; each against a swap-loop instance fed in step with it.
-    for (int pass = simd ? 0 : 2; pass < 3; ++pass) {
-        for (size_t i = 0; i < cases.size(); ++i) fails += !check(cases[i], pass == 0 && (i < 6 || i + 1 == cases.size()), pass == 1, pass == 0);
-        printf("%zu cases (%s), %d failed so far\n", cases.size(),
-               pass == 0 ? "hand-over on" : pass == 1 ? "hand-over off, AVX2 flip tests" : "hand-over off, scalar flip tests", fails);
+    // legs: the hand-over with the deferred star (the default path; it needs AVX2) compared after every insert and
+    // only at the end, the hand-over with a ring pass per insert, then the generic cavity walk with the batched AVX2
+    // flip tests and with the scalar ones; each against a swap-loop instance fed in step with it.
+    static const char *const leg[5] = {"hand-over on, star deferred", "hand-over on, star deferred, compared at the end only",
+                                       "hand-over on, ring pass per insert", "hand-over off, AVX2 flip tests",
+                                       "hand-over off, scalar flip tests"};
+    for (int pass = simd ? 0 : 4; pass < 5; ++pass) {
+        for (size_t i = 0; i < cases.size(); ++i)
+            fails += !check(cases[i], pass == 0 && (i < 6 || i + 1 == cases.size()), pass == 3, pass <= 2, pass <= 1, pass != 1);
+        printf("%zu cases (%s), %d failed so far\n", cases.size(), leg[pass], fails);
     }
     if (path) {
-        uint64_t hh = 0, ha = 0, hs = 0, hr = 0;
-        const double th = time_inserts(file, false, false, true, hh), ta = time_inserts(file, false, simd, false, ha),
-                     ts = time_inserts(file, false, false, false, hs), tr = time_inserts(file, true, false, false, hr);
-        printf("%s inserts: hand-over %.2f ms, cavity+%s %.2f ms, cavity+scalar %.2f ms, swap loop %.2f ms (x%.2f); facet-edge hash %016llx %s\n",
-               path, th, simd ? "AVX2" : "scalar", ta, ts, tr, tr / th, (unsigned long long)hh,
-               hh == hr && ha == hr && hs == hr ? "equal" : "DIFFERENT");
-        if (hh != hr || ha != hr || hs != hr) fails++;
+        uint64_t hd = 0, hh = 0, ha = 0, hs = 0, hr = 0;
+        const double td = time_inserts(file, false, false, true, true, hd), th = time_inserts(file, false, false, true, false, hh),
+                     ta = time_inserts(file, false, simd, false, false, ha), ts = time_inserts(file, false, false, false, false, hs),
+                     tr = time_inserts(file, true, false, false, false, hr);
+        const bool eq = hd == hr && hh == hr && ha == hr && hs == hr;
+        printf("%s inserts: deferred %.2f ms, hand-over %.2f ms, cavity+%s %.2f ms, cavity+scalar %.2f ms, swap loop %.2f ms (x%.2f); "
+               "facet-edge hash %016llx %s\n",
+               path, td, th, simd ? "AVX2" : "scalar", ta, ts, tr, tr / td, (unsigned long long)hd, eq ? "equal" : "DIFFERENT");
+        if (!eq) fails++;
     }
     return fails ? 1 : 0;
 }

@@ -28,9 +28,12 @@ int main(int argc, char **argv) {
     const float rw = (float)(std::abs(b[1] - b[0]) + 2.0), rh = (float)(std::abs(b[3] - b[2]) + 2.0);
     double best = 1e30, best_ticks_per_ms = 0;
     uint64_t hash = 0;
-    long n_cavity = 0, n_handover = 0, n_ho_bail = 0, n_loop = 0;
+    long n_cavity = 0, n_handover = 0, n_ho_bail = 0, n_loop = 0, n_deferred = 0, n_ho_pocket = 0;
 #ifdef AOS_SD_HANDOVER   // (a variant built against an older subdiv2d.h has no hand-over)
     const bool handover = !getenv("AOS_SD_NO_HANDOVER");   // (set: the generic cavity walk only)
+#endif
+#ifdef AOS_SD_DEFERRED   // (likewise: an older subdiv2d.h has no deferred star)
+    const bool deferred = !getenv("AOS_SD_NO_DEFERRED");   // (set: a ring pass per insert)
 #endif
     aos::SdProf bestp{};
     for (int rep = 0; rep < reps; ++rep) {
@@ -40,6 +43,9 @@ int main(int argc, char **argv) {
         aos::Subdiv2D sd;
 #ifdef AOS_SD_HANDOVER
         sd.set_handover(handover);
+#endif
+#ifdef AOS_SD_DEFERRED
+        sd.set_deferred(deferred);
 #endif
         sd.reserve(n);
         const auto t0 = std::chrono::steady_clock::now();
@@ -64,18 +70,27 @@ int main(int argc, char **argv) {
 #ifdef AOS_SD_HANDOVER
         n_handover = sd.n_handover; n_ho_bail = sd.n_ho_bail;
 #endif
+#ifdef AOS_SD_DEFERRED
+        n_deferred = sd.n_deferred; n_ho_pocket = sd.n_ho_pocket;
+#endif
         std::vector<float> e;
         sd.voronoi_edges(e);
         hash = 1469598103934665603ull;
         for (float v : e) { uint32_t u; memcpy(&u, &v, 4); hash = (hash ^ u) * 1099511628211ull; }
     }
-    printf("inserts %d: best %.2f ms of %d; facet-edge hash %016llx; cavity %ld (hand-over %ld, bailed out %ld), swap loop %ld", n, best, reps,
-           (unsigned long long)hash, n_cavity, n_handover, n_ho_bail, n_loop);
+    printf("inserts %d: best %.2f ms of %d; facet-edge hash %016llx; cavity %ld (hand-over %ld, deferred %ld, bailed out %ld, pockets %ld), "
+           "swap loop %ld", n, best, reps, (unsigned long long)hash, n_cavity, n_handover, n_deferred, n_ho_bail, n_ho_pocket, n_loop);
 #ifdef AOS_SD_PROF
     const double k = 1.0 / best_ticks_per_ms;   // ticks -> ms
     printf(" | locate %.2f ms (%.2f steps/insert), dfs %.2f ms (%.2f steps/insert), write %.2f ms, rest %.2f ms",
            bestp.t_locate * k, (double)bestp.loc_iters / n, bestp.t_dfs * k, (double)bestp.dfs_steps / n, bestp.t_write * k,
            best - (bestp.t_locate + bestp.t_dfs + bestp.t_write) * k);
+#ifdef AOS_SD_DEFERRED
+    printf(" | locates on the pending star %llu, ended there %llu (%.2f steps each incl. those that left); retired rings %.1f slots, "
+           "%.2f kept their spoke",
+           bestp.star_loc, bestp.star_found, bestp.star_loc ? (double)bestp.star_steps / bestp.star_loc : 0.0,
+           n_handover ? (double)bestp.ring_slots / n_handover : 0.0, n_handover ? (double)bestp.kept_slots / n_handover : 0.0);
+#endif
 #endif
     printf("\n");
     return 0;
