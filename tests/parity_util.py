@@ -44,6 +44,26 @@ def assert_gvd_parity(g: dict, o: dict):
         assert np.array_equal(g[k], o[k]), k
 
 
+def assert_gvd_full_parity(ctx, g: dict, o: dict):
+    """assert_gvd_parity plus what it leaves out: the merged seeds, the rows' label points and the markers' cells
+    of ctx's last GVD call (g its graph), bit for bit against the oracle result o (run with markers = 1)."""
+    assert_gvd_parity(g, o)
+    if not o["published"]:
+        return
+    assert g["n_merged"] == len(o["merged"]), (g["n_merged"], len(o["merged"]))
+    m = ctx.gvd_markers()
+    assert m["seeds"].shape == o["merged"].shape, (m["seeds"].shape, o["merged"].shape)
+    assert np.array_equal(m["seeds"], o["merged"], equal_nan=True), "merged seeds differ"
+    assert m["row_label_valid"].shape == o["row_label_valid"].shape, \
+        (m["row_label_valid"].shape, o["row_label_valid"].shape)
+    assert np.array_equal(m["row_label_valid"], o["row_label_valid"]), "row label validity differs"
+    v = o["row_label_valid"].astype(bool)
+    assert np.array_equal(m["row_label_pts"][v], o["row_label_pts"][v], equal_nan=True), "row label points differ"
+    for k in ("cell_offsets", "cell_xy", "cell_center", "cell_rgba"):
+        assert m[k].shape == o[k].shape, (k, m[k].shape, o[k].shape)
+        assert np.array_equal(m[k], o[k], equal_nan=True), f"markers' {k} differ"
+
+
 def sha_of(a, dt):
     """SHA-256 of an array as tools/make_golden.py hashes it (dtype, shape, bytes)."""
     import hashlib
