@@ -1,7 +1,12 @@
 // Host Delaunay with cv::Subdiv2D semantics — see subdiv2d.h. Compiled -ffp-contract=off.
 #include "subdiv2d.h"
 
+#if defined(__x86_64__)
 #include <immintrin.h>
+#define AOS_AVX2 __attribute__((target("avx2")))
+#else
+#define AOS_AVX2
+#endif
 
 #include <algorithm>
 #include <cfloat>
@@ -51,6 +56,49 @@ inline bool voronoi_point(float o0x, float o0y, float d0x, float d0y, float o1x,
     }
     return false;
 }
+
+// The swap loop's flip test of a link edge O -> D whose right triangle has the apex T, against the new point P:
+//   isRightOf(T, edge) > 0 && isPtInCircle3(pt = O, a = T, b = D, c = P) < 0, eps = FLT_EPSILON / 8.
+// Every operand has x, y and n2 = x*x + y*y as exact double copies of the float coordinates (the float -> double
+// conversions are exact, so every product and sum rounds as in triangleArea / isPtInCircle3, and |p|^2 is formed once
+// per vertex in the same order). This is the one scalar statement of the test: bit-exactness against OpenCV rests on
+// these operands in this operation order. It is evaluated whole and combined without a branch: the orientation test
+// is nearly always true and the in-circle sum's operands are already loaded; the sum is only compared, so where the
+// orientation fails the result is false whatever the sum is.
+template <class TT, class TO, class TD, class TP>
+inline bool flips(const TT &T, const TO &O, const TD &D, const TP &P) {
+    auto area = [](const auto &a, const auto &b, const auto &c) { return (b.x - a.x) * (c.y - a.y) - (b.y - a.y) * (c.x - a.x); };
+    const double aTDO = area(T, D, O);
+    double val = T.n2 * area(D, P, O);
+    val -= D.n2 * area(T, P, O);
+    val += P.n2 * aTDO;
+    val -= O.n2 * area(T, D, P);
+    return (aTDO > 0) & (val < -(FLT_EPSILON * 0.125));
+}
+struct HoS { double x, y, n2; };   // an operand of flips() put together from the ring arrays
+
+#if defined(__x86_64__)
+// Four flip tests at once (bit i = lane i swaps): each lane is flips(), the same plain IEEE double subtractions,
+// products and sums in the same order, no FMA.
+struct HoV { __m256d x, y, n; };
+AOS_AVX2 inline HoV ho_ld(const double *x, const double *y, const double *n, int i) {
+    return HoV{_mm256_loadu_pd(x + i), _mm256_loadu_pd(y + i), _mm256_loadu_pd(n + i)};
+}
+AOS_AVX2 inline __m256d area4(__m256d ax, __m256d ay, __m256d bx, __m256d by, __m256d cx, __m256d cy) {
+    return _mm256_sub_pd(_mm256_mul_pd(_mm256_sub_pd(bx, ax), _mm256_sub_pd(cy, ay)),
+                         _mm256_mul_pd(_mm256_sub_pd(by, ay), _mm256_sub_pd(cx, ax)));
+}
+AOS_AVX2 inline int ho_test4(const HoV &T, const HoV &O, const HoV &D, const HoV &P) {
+    const __m256d aTDO = area4(T.x, T.y, D.x, D.y, O.x, O.y);
+    __m256d val = _mm256_mul_pd(T.n, area4(D.x, D.y, P.x, P.y, O.x, O.y));
+    val = _mm256_sub_pd(val, _mm256_mul_pd(D.n, area4(T.x, T.y, P.x, P.y, O.x, O.y)));
+    val = _mm256_add_pd(val, _mm256_mul_pd(P.n, aTDO));
+    val = _mm256_sub_pd(val, _mm256_mul_pd(O.n, area4(T.x, T.y, D.x, D.y, P.x, P.y)));
+    const __m256d right = _mm256_cmp_pd(aTDO, _mm256_setzero_pd(), _CMP_GT_OQ);
+    const __m256d inside = _mm256_cmp_pd(val, _mm256_set1_pd(-(FLT_EPSILON * 0.125)), _CMP_LT_OQ);
+    return _mm256_movemask_pd(_mm256_and_pd(right, inside));
+}
+#endif
 }  // namespace
 
 void Subdiv2D::reserve(size_t n) {
@@ -124,8 +172,6 @@ void Subdiv2D::delete_edge(int e) {   // deleteEdge
     free_q = q;
 }
 
-// The batched AVX2 tests are exact but not faster on the EPYC 9575F host (the 4 x 4 transposes take
-// the FP pipes the scalar tests use): off by default, kept for tools/sdcheck and set_simd().
 Subdiv2D::Subdiv2D() = default;
 
 void Subdiv2D::init_delaunay(float rx, float ry, float rw, float rh, int rect_mode) {
@@ -226,10 +272,7 @@ bool Subdiv2D::insert(float x, float y) {
     }
     if (curr_edge == 0) return false;  // CV_Assert
     curr_point = new_point(x, y, 0);
-    if (loc == 0 && !force_loop &&
-        (use_ho     ? insert_cavity_ho(curr_edge, curr_point)
-         : use_avx2 ? insert_cavity<true>(curr_edge, curr_point)
-                    : insert_cavity<false>(curr_edge, curr_point))) {
+    if (loc == 0 && !force_loop && insert_cavity(curr_edge, curr_point)) {
         ++n_cavity;
         return true;
     }
@@ -251,25 +294,11 @@ bool Subdiv2D::insert(float x, float y) {
 // OpenCV's swap loop (Subdiv2D::insert after the connects), the reference path.
 void Subdiv2D::swap_loop(int curr_edge, int first_point, int curr_point) {
     const int max_edges = (int)rec.size() * 4;
-    // Swap loop with the predicates written out on exact double copies of the float coordinates
-    // (the float -> double conversions are exact, so every product and sum rounds as in
-    // triangleArea / isPtInCircle3, and |p|^2 is formed once per vertex in the same order).
     const V2d P = vd[curr_point];
-    auto area = [](const V2d &a, const V2d &b, const V2d &c) { return (b.x - a.x) * (c.y - a.y) - (b.y - a.y) * (c.x - a.x); };
     for (int i = 0; i < max_edges; i++) {
         const int temp = oprev(curr_edge);
-        const int tdst = dst(temp), corg = org(curr_edge), cdst = dst(curr_edge);
-        const V2d &T = vd[tdst], &O = vd[corg], &D = vd[cdst];
-        bool flip = false;
-        if (area(T, D, O) > 0) {   // isRightOf(temp_dst, curr_edge) > 0
-            // isPtInCircle3(pt = org, a = temp_dst, b = dst, c = new point) < 0, eps = FLT_EPSILON / 8
-            double val = T.n2 * area(D, P, O);
-            val -= D.n2 * area(T, P, O);
-            val += P.n2 * area(T, D, O);
-            val -= O.n2 * area(T, D, P);
-            flip = val < -(FLT_EPSILON * 0.125);
-        }
-        if (flip) {
+        const int corg = org(curr_edge);
+        if (flips(vd[dst(temp)], vd[corg], vd[dst(curr_edge)], P)) {
             swap_edge(curr_edge);
             curr_edge = oprev(curr_edge);
         } else if (corg == first_point) {
@@ -280,208 +309,7 @@ void Subdiv2D::swap_loop(int curr_edge, int first_point, int curr_point) {
     }
 }
 
-// The swap loop's flip test for link edges es[0..n) (n <= 4) against the new point P, written into
-// out[] (1 = swap): isRightOf(temp_dst, e) > 0 && isPtInCircle3(org, temp_dst, dst, P) < -eps, with
-// temp_dst = Dst(Oprev e). Same operands and operation order as swap_loop in every lane.
-void Subdiv2D::flip_tests_scalar(const int *es, int n, const V2d &P, int *out) const {
-    auto area = [](const V2d &a, const V2d &b, const V2d &c) { return (b.x - a.x) * (c.y - a.y) - (b.y - a.y) * (c.x - a.x); };
-    for (int i = 0; i < n; ++i) {
-        const int e = es[i];
-        const V2d &T = vd[dst(oprev(e))], &O = vd[org(e)], &D = vd[dst(e)];
-        bool flip = false;
-        if (area(T, D, O) > 0) {
-            double val = T.n2 * area(D, P, O);
-            val -= D.n2 * area(T, P, O);
-            val += P.n2 * area(T, D, O);
-            val -= O.n2 * area(T, D, P);
-            flip = val < -(FLT_EPSILON * 0.125);
-        }
-        out[i] = flip;
-    }
-}
-
-// Four tests at once on AVX2 (one lane each; every lane rounds exactly like the scalar form: plain
-// IEEE double sub / mul in the same order, no FMA).
-#define AOS_AVX2 __attribute__((target("avx2")))
-AOS_AVX2 static inline void transpose3(const __m256d *r, __m256d &X, __m256d &Y, __m256d &N) {
-    const __m256d t0 = _mm256_unpacklo_pd(r[0], r[1]), t1 = _mm256_unpackhi_pd(r[0], r[1]);
-    const __m256d t2 = _mm256_unpacklo_pd(r[2], r[3]), t3 = _mm256_unpackhi_pd(r[2], r[3]);
-    X = _mm256_permute2f128_pd(t0, t2, 0x20);
-    N = _mm256_permute2f128_pd(t0, t2, 0x31);
-    Y = _mm256_permute2f128_pd(t1, t3, 0x20);
-}
-AOS_AVX2 static inline __m256d area4(__m256d ax, __m256d ay, __m256d bx, __m256d by, __m256d cx, __m256d cy) {
-    return _mm256_sub_pd(_mm256_mul_pd(_mm256_sub_pd(bx, ax), _mm256_sub_pd(cy, ay)),
-                         _mm256_mul_pd(_mm256_sub_pd(by, ay), _mm256_sub_pd(cx, ax)));
-}
-
-AOS_AVX2 void Subdiv2D::flip_tests_avx2(const int *es, int n, const V2d &P, int *out) const {
-    __m256d rT[4], rO[4], rD[4];
-    for (int i = 0; i < 4; ++i) {
-        const int e = es[i < n ? i : 0];
-        rT[i] = _mm256_loadu_pd(&vd[dst(oprev(e))].x);
-        rO[i] = _mm256_loadu_pd(&vd[org(e)].x);
-        rD[i] = _mm256_loadu_pd(&vd[dst(e)].x);
-    }
-    __m256d Tx, Ty, Tn, Ox, Oy, On, Dx, Dy, Dn;
-    transpose3(rT, Tx, Ty, Tn);
-    transpose3(rO, Ox, Oy, On);
-    transpose3(rD, Dx, Dy, Dn);
-    const __m256d Px = _mm256_set1_pd(P.x), Py = _mm256_set1_pd(P.y), Pn = _mm256_set1_pd(P.n2);
-    const __m256d aTDO = area4(Tx, Ty, Dx, Dy, Ox, Oy);
-    __m256d val = _mm256_mul_pd(Tn, area4(Dx, Dy, Px, Py, Ox, Oy));
-    val = _mm256_sub_pd(val, _mm256_mul_pd(Dn, area4(Tx, Ty, Px, Py, Ox, Oy)));
-    val = _mm256_add_pd(val, _mm256_mul_pd(Pn, aTDO));
-    val = _mm256_sub_pd(val, _mm256_mul_pd(On, area4(Tx, Ty, Dx, Dy, Px, Py)));
-    const __m256d right = _mm256_cmp_pd(aTDO, _mm256_setzero_pd(), _CMP_GT_OQ);
-    const __m256d inside = _mm256_cmp_pd(val, _mm256_set1_pd(-(FLT_EPSILON * 0.125)), _CMP_LT_OQ);
-    const int mask = _mm256_movemask_pd(_mm256_and_pd(right, inside));
-    for (int i = 0; i < n; ++i) out[i] = (mask >> i) & 1;
-}
-
-// The ring pass of insert_cavity over plain restrict pointers (the Rec / V2d layouts as ints: a record is on[2],
-// op[2], org[2], link, pad; a vertex's spoke sits at int 7 of its 32 bytes): one pass over the boundary L_k
-// (k in walk order) writes every field of spoke S_k = x_k -> p (on / op / org in both directions), the two ring
-// links of the boundary edges next to it and vtx[x_k].firstEdge = S_k. In a function of its own the compiler keeps
-// the loop's values in registers (round 5 on the box: the replay's write phase 7.9 -> 5.3 ms with the certification
-// change below, profiles/r05s_sdprof.txt).
-__attribute__((noinline)) static void ring_pass(int *__restrict R, int *__restrict vfirst, const int *__restrict spoke,
-                                                const int *__restrict bd, const int *__restrict bu, int m, int p) {
-    // directed edge e's fields at R[2 e] (onext), R[2 e + 1] (oprev), R[2 e + 2] (origin)
-    auto sp = [&](int x) { return spoke[8 * (size_t)x]; };
-    int Sm = sp(bu[m - 1]), S = sp(bu[0]);
-    for (int k = 0; k < m; ++k) {
-        const int k1 = k + 1 == m ? 0 : k + 1;
-        const int L = bd[k], Ln = bd[k1], x = bu[k], Sn = sp(bu[k1]);
-        const int sLn = Ln ^ 2, sS = S ^ 2;
-        R[2 * (ptrdiff_t)L] = S;                                       // Onext(L_k) = S_k
-        R[2 * (ptrdiff_t)sLn + 1] = S;                                 // Oprev(Sym L_k+1) = S_k
-        int *a = R + 2 * (ptrdiff_t)S, *b = R + 2 * (ptrdiff_t)sS;
-        a[0] = sLn; a[1] = L; a[2] = x;                                // S_k: x_k -> p
-        b[0] = Sm ^ 2; b[1] = Sn ^ 2; b[2] = p;                        // Sym S_k: around p, counter-clockwise
-        vfirst[x] = S;
-        Sm = S; S = Sn;
-    }
-}
-
-// Cavity form of an INSIDE insert (subdiv2d.h). e0 = locate's edge: p lies left of it, inside the
-// triangle (e0, Lnext e0, Lnext^2 e0). Returns false, having changed nothing but the scratch, when
-// the DFS cannot certify the cavity; the caller then runs the connects and the swap loop.
-template <bool SIMD>
-bool Subdiv2D::insert_cavity(int e0, int p) {
-    // the marks live in the vertex's own line (V2d::stamp / spoke): the DFS reads them right after the
-    // vertex's coordinates (C2 replay 25.3-26.1 -> 25.1-25.9 ms on the box, profiles/r04z_replay_dfs.txt)
-    if (++stamp >= (1 << 29)) { for (V2d &x : vd) x.stamp = 0; stamp = 1; }
-    const int sA = 2 * stamp;   // this insert's mark: a cavity vertex (the three corners and every apex)
-    const int eB = lnext(e0), eA = lnext(eB);          // root link edges in walk order: eA, eB, e0
-    if (lnext(eA) != e0) return false;
-    const int first = org(e0), v1 = org(eB), v2 = org(eA);
-    if (first == v1 || v1 == v2 || v2 == first) return false;
-    vd[first].stamp = vd[v1].stamp = vd[v2].stamp = sA;
-
-    const V2d P = vd[p];
-    auto area = [](const V2d &a, const V2d &b, const V2d &c) { return (b.x - a.x) * (c.y - a.y) - (b.y - a.y) * (c.x - a.x); };
-    // scratch sized for the worst case: every swap adds one apex, one stacked edge and one boundary edge
-    const size_t cap = vp.size() + 8;
-    if (dfs_stack.size() < cap) {
-        dfs_stack.resize(2 * cap); cav_bnd.resize(2 * cap);
-        cav_bu.resize(2 * cap);
-    }
-    int *const stk = dfs_stack.data(), *const bd = cav_bnd.data(), *const bu = cav_bu.data();
-    // The stack and the boundary lists are bumped pointers and no flip counter is kept (last_flip < 0: no flip): with
-    // fewer live values the walk keeps them in registers (the flip path had reloaded four spilled base pointers and
-    // incremented a counter in memory; round 5 on the box: walk 11.7-13.3 -> 10.5-10.6 ms, the C2 replay 17.0-17.7 ->
-    // 15.8-16.2 ms, profiles/r05zq_sdprof.txt).
-    int *top = stk, *bdp = bd, *bup = bu;
-    int last_flip = -1;
-    *top++ = e0; *top++ = eB;
-    int e = eA;
-    // Pre-order walk; every test reads the old triangle right of the link edge (never incident to p).
-    // The first child (w -> v) is walked at once; the second (u -> w) waits on the stack. Once the walk
-    // reaches a boundary edge it pops the stacked edges, whose tests are independent of each other (the SIMD
-    // instantiation, off by default, evaluates them four at a time until one swaps).
-    // The test is evaluated whole and combined without a branch: the orientation test is nearly always true
-    // and the in-circle sum's operands are already loaded (box A/B: 28.0-28.6 -> 26.1-26.5 ms for the C2
-    // seeds together with the SIMD batches compiled out of the default path, profiles/r04z_replay_dfs.txt).
-    int known = -1;   // 1: e is known to swap (decided in a batch; SIMD only)
-    SDP_T0(t_dfs);
-    for (;;) {
-        SDP_INC(dfs_steps);
-        const int t = oprev(e), w = dst(t);
-        bool flip;
-        if (SIMD && known == 1) {
-            flip = true;
-        } else {
-            const V2d &T = vd[w], &O = vd[org(e)], &D = vd[dst(e)];
-            const double aTDO = area(T, D, O);   // same expressions and order as swap_loop
-            double val = T.n2 * area(D, P, O);
-            val -= D.n2 * area(T, P, O);
-            val += P.n2 * aTDO;
-            val -= O.n2 * area(T, D, P);
-            flip = (aTDO > 0) & (val < -(FLT_EPSILON * 0.125));
-        }
-        known = -1;
-        if (flip) {
-            // the cavity would wrap a vertex. (w is never p: p has no edge yet. The scratch cannot overflow: every
-            // swap adds a distinct vertex, so the swaps are fewer than the vertices <= cap - 8.)
-            V2d &W = vd[w];
-            if (W.stamp == sA) return false;
-            W.stamp = sA;
-            W.spoke = e;                                       // e becomes w -> p
-            last_flip = e;
-            *top++ = t;                                        // u -> w, after the w -> v subtree
-            e = sym(onext(sym(e)));                            // w -> v
-            continue;
-        }
-        *bdp++ = e; *bup++ = org(e);
-        if (SIMD) {
-            int d[4];
-            while (top - stk >= 4) {
-                const int b[4] = {top[-1], top[-2], top[-3], top[-4]};
-                flip_tests_avx2(b, 4, P, d);
-                int i = 0;
-                for (; i < 4 && !d[i]; ++i) {
-                    const int x = b[i];
-                    *bdp++ = x; *bup++ = org(x);
-                }
-                top -= i;
-                if (i < 4) { known = 1; break; }
-            }
-        }
-        if (top == stk) break;
-        e = *--top;
-    }
-    const int nb = (int)(bdp - bd);
-    SDP_ADD(t_dfs, t_dfs);
-    SDP_T0(t_wr);
-    // Why no certification of the boundary is needed (round 4 checked it after the walk): by induction over the walk,
-    // a tested edge u -> v emits boundary edges forming a chain from v back to u (a leaf emits itself; a swapped
-    // edge with apex w emits the chain of w -> v, then that of u -> w), whose origins are u and the apexes below it.
-    // So the three root chains always close into one cycle of 3 + (swaps) edges, and its vertices are distinct exactly
-    // when every apex is new, which the walk checks at each swap (the C2 replay 25.6-26.4 -> 22.6-23.1 ms on the
-    // box with ring_pass; tools/sdcheck still compares every insert's full state with the swap loop).
-    const int m = nb;
-    // ---- the outcome. OpenCV's two connectEdges (after the first newEdge + splice) number the three new quad-edges
-    // first -> p, v1 -> p, v2 -> p in that order; everything else they write (the rings of first, v1, v2 and p next to
-    // the new edges, their end points, firstEdge) is rewritten by ring_pass, which sets every field of every spoke and
-    // the ring links of the boundary edges on both sides of it. So only their allocations are kept (the C2 replay
-    // 22.6-23.1 -> 21.8-22.2 ms on the box; tools/sdcheck: identical full state after every insert).
-    const int c0 = new_edge(), c1 = new_edge(), c2 = new_edge();   // first -> p, v1 -> p, v2 -> p
-    vd[first].spoke = c0; vd[v1].spoke = c1; vd[v2].spoke = c2;
-    vfirst[p] = sym(last_flip >= 0 ? last_flip : c2);   // the last setEdgePoints with p as destination
-    // swapEdges' setEdgePoints(e, apex, p) and vtx[apex].firstEdge = e, and the rings of the final star: ring_pass
-    static_assert(sizeof(Rec) == 32 && sizeof(Half) == 16 && offsetof(Half, op) == 4 && offsetof(Half, org) == 8, "ring_pass: Rec layout");
-    static_assert(sizeof(V2d) == 32 && offsetof(V2d, spoke) == 28, "ring_pass: V2d layout");
-    ring_pass(ri(), vfirst.data(), &vd[0].spoke, bd, bu, m, p);
-    SDP_ADD(t_write, t_wr);
-    return true;
-}
-
-// ---- hand-over: the previous insert's star as arrays (subdiv2d.h) ----
-#if defined(__x86_64__)
-#ifndef AOS_HO_VEC
-#define AOS_HO_VEC 1   // 0: every hand-over test and copy one slot at a time (the A/B of DESIGN.md 6.1)
-#endif
+// ---- the ring of an insert's star as arrays (subdiv2d.h) ----
 static constexpr int HO_PAD = 4;   // spare entries before slot 0 and after slot cap - 1 (one of each is the cyclic copy)
 
 Subdiv2D::RingP Subdiv2D::ring_ptrs(Ring &r) {
@@ -499,31 +327,59 @@ void Subdiv2D::ring_reserve(Ring &r, int slots) {   // keeps the contents
     r.cap = cap;
 }
 
-// ring_pass reading the spokes from the ring's own array (sp[k] = S_k, with bd / sp padded cyclically at m); it also
-// leaves slot k in the spare int of L_k's half record, which is how the next insert finds its fan triangle's slot.
-__attribute__((noinline)) static void ring_pass_ho(int *__restrict R, int *__restrict vfirst, const int *__restrict bd,
-                                                   const int *__restrict bu, const int *__restrict sp, int m, int p) {
+// The one statement of what slot k of a ring around p owns in the records, and so of what is pending while its star
+// is deferred (subdiv2d.h): f(field, value) for Onext(L_k), the slot int of L_k (how the next insert finds its fan
+// triangle's slot), Oprev(Sym L_k+1), every field of the spoke S_k = x_k -> p and of Sym S_k, and firstEdge of x_k.
+// L = L_k, Ln = L_k+1, x = x_k, Sm / S / Sn = S_k-1 / S_k / S_k+1. R is the Rec array as ints (a directed edge e's
+// fields at R[2 e]: onext, oprev, origin, slot). The ring pass, retire() and for_pending() all go through it.
+template <class F>
+static inline void slot_fields(int *R, int *vfirst, int k, int L, int Ln, int x, int Sm, int S, int Sn, int p, F f) {
+    const int sLn = Ln ^ 2, sS = S ^ 2;
+    f(R[2 * (ptrdiff_t)L], S);                                     // Onext(L_k) = S_k
+    f(R[2 * (ptrdiff_t)L + 3], k);                                 // slot of L_k
+    f(R[2 * (ptrdiff_t)sLn + 1], S);                               // Oprev(Sym L_k+1) = S_k
+    int *a = R + 2 * (ptrdiff_t)S, *b = R + 2 * (ptrdiff_t)sS;
+    f(a[0], sLn); f(a[1], L); f(a[2], x);                          // S_k: x_k -> p
+    f(b[0], Sm ^ 2); f(b[1], Sn ^ 2); f(b[2], p);                  // Sym S_k: around p, counter-clockwise
+    f(vfirst[x], S);
+}
+static inline void slot_write(int *R, int *vfirst, int k, int L, int Ln, int x, int Sm, int S, int Sn, int p) {
+    slot_fields(R, vfirst, k, L, Ln, x, Sm, S, Sn, p, [](int &field, int v) { field = v; });
+}
+
+// The ring pass: one pass over the boundary L_k (k in walk order; bd / sp padded cyclically at m) writes every slot's
+// fields. OpenCV's swapEdges' setEdgePoints(e, apex, p) and vtx[apex].firstEdge = e, and the rings of the final star,
+// are all in it. In a function of its own over plain restrict pointers the compiler keeps the loop's values (the
+// carried S_k-1, S_k, S_k+1) in registers.
+__attribute__((noinline)) static void ring_pass(int *__restrict R, int *__restrict vfirst, const int *__restrict bd,
+                                                const int *__restrict bu, const int *__restrict sp, int m, int p) {
     int Sm = sp[m - 1], S = sp[0];
     for (int k = 0; k < m; ++k) {
-        const int L = bd[k], Ln = bd[k + 1], x = bu[k], Sn = sp[k + 1];
-        const int sLn = Ln ^ 2, sS = S ^ 2;
-        R[2 * (ptrdiff_t)L] = S;                                       // Onext(L_k) = S_k
-        R[2 * (ptrdiff_t)L + 3] = k;                                   // slot of L_k
-        R[2 * (ptrdiff_t)sLn + 1] = S;                                 // Oprev(Sym L_k+1) = S_k
-        int *a = R + 2 * (ptrdiff_t)S, *b = R + 2 * (ptrdiff_t)sS;
-        a[0] = sLn; a[1] = L; a[2] = x;                                // S_k: x_k -> p
-        b[0] = Sm ^ 2; b[1] = Sn ^ 2; b[2] = p;                        // Sym S_k: around p, counter-clockwise
-        vfirst[x] = S;
+        const int Sn = sp[k + 1];
+        slot_write(R, vfirst, k, bd[k], bd[k + 1], bu[k], Sm, S, Sn, p);
         Sm = S; S = Sn;
     }
 }
 
-// The generic pre-order walk of insert_cavity from one link edge e, with a stack of its own; every leaf goes into
-// ring N at slot q with its apex and both vertices' coordinates. Returns the next free slot, or -1 when an apex is
-// already a cavity vertex; the last swap (or last_flip, if there was none) is left in ho_lf.
-__attribute__((noinline)) int Subdiv2D::ho_walk(int e, const V2d &Pin, int sA, Ring &N, int q, int last_flip) {
+// The cavity walk from one link edge e (the generic form: the swap loop's tests read off the records); every leaf
+// goes into ring N at slot q with its apex and both vertices' coordinates. Returns the next free slot, or -1 when an
+// apex is already a cavity vertex (the cavity would wrap a vertex: the caller runs the connects and the swap loop);
+// the last swap (or last_flip, if there was none) is left in ho_lf.
+//  * Pre-order: the first child (w -> v) is walked at once, the second (u -> w) waits on the stack, which is the swap
+//    loop's order. Every test reads the old triangle right of the link edge, never one incident to p, so the walk
+//    changes no record.
+//  * The marks live in the vertex's own line (V2d::stamp / spoke): the walk reads them right after the vertex's
+//    coordinates. w is never p (p has no edge yet), and the stack cannot overflow: every swap adds a distinct vertex,
+//    so the swaps are fewer than the vertices (dfs_stack is sized by them).
+//  * Why no certification of the boundary is needed: by induction over the walk, a tested edge u -> v emits leaves
+//    forming a chain from v back to u (a leaf emits itself; a swapped edge with apex w emits the chain of w -> v, then
+//    that of u -> w), whose origins are u and the apexes below it. So the three root chains always close into one
+//    cycle of 3 + (swaps) edges, and its vertices are distinct exactly when every apex is new, which is checked at
+//    each swap. (tools/sdcheck still compares every insert's full state with the swap loop.)
+//  * The stack is a bumped pointer and no flip counter is kept (last_flip < 0: no flip): with fewer live values the
+//    walk keeps them in registers.
+__attribute__((noinline)) int Subdiv2D::cavity_walk(int e, const V2d &Pin, int sA, Ring &N, int q, int last_flip) {
     const V2d P = Pin;
-    auto area = [](const V2d &a, const V2d &b, const V2d &c) { return (b.x - a.x) * (c.y - a.y) - (b.y - a.y) * (c.x - a.x); };
     int *const stk = dfs_stack.data();
     int *top = stk;
     RingP n = ring_ptrs(N);
@@ -532,13 +388,8 @@ __attribute__((noinline)) int Subdiv2D::ho_walk(int e, const V2d &Pin, int sA, R
     for (;;) {
         SDP_INC(dfs_steps);
         const int t = oprev(e), w = dst(t), o = org(e);
-        const V2d &T = vd[w], &O = vd[o], &D = vd[dst(e)];
-        const double aTDO = area(T, D, O);   // same expressions and order as swap_loop
-        double val = T.n2 * area(D, P, O);
-        val -= D.n2 * area(T, P, O);
-        val += P.n2 * aTDO;
-        val -= O.n2 * area(T, D, P);
-        if ((aTDO > 0) & (val < -(FLT_EPSILON * 0.125))) {
+        const V2d &T = vd[w], &O = vd[o];
+        if (flips(T, O, vd[dst(e)], P)) {
             V2d &W = vd[w];
             if (W.stamp == sA) return -1;
             // a ring vertex of the pending star outside the cavity: the child edges may be Sym L_i (subdiv2d.h)
@@ -562,33 +413,12 @@ __attribute__((noinline)) int Subdiv2D::ho_walk(int e, const V2d &Pin, int sA, R
     return q;
 }
 
-namespace {
-struct HoV { __m256d x, y, n; };
-AOS_AVX2 inline HoV ho_ld(const double *x, const double *y, const double *n, int i) {
-    return HoV{_mm256_loadu_pd(x + i), _mm256_loadu_pd(y + i), _mm256_loadu_pd(n + i)};
-}
-// four flip tests (bit i = lane i swaps); every lane runs swap_loop's subtractions, products and sums in its order
-AOS_AVX2 inline int ho_test4(const HoV &T, const HoV &O, const HoV &D, const HoV &P) {
-    const __m256d aTDO = area4(T.x, T.y, D.x, D.y, O.x, O.y);
-    __m256d val = _mm256_mul_pd(T.n, area4(D.x, D.y, P.x, P.y, O.x, O.y));
-    val = _mm256_sub_pd(val, _mm256_mul_pd(D.n, area4(T.x, T.y, P.x, P.y, O.x, O.y)));
-    val = _mm256_add_pd(val, _mm256_mul_pd(P.n, aTDO));
-    val = _mm256_sub_pd(val, _mm256_mul_pd(O.n, area4(T.x, T.y, D.x, D.y, P.x, P.y)));
-    const __m256d right = _mm256_cmp_pd(aTDO, _mm256_setzero_pd(), _CMP_GT_OQ);
-    const __m256d inside = _mm256_cmp_pd(val, _mm256_set1_pd(-(FLT_EPSILON * 0.125)), _CMP_LT_OQ);
-    return _mm256_movemask_pd(_mm256_and_pd(right, inside));
-}
-struct HoS { double x, y, n; };
-inline bool ho_test1(const HoS &T, const HoS &O, const HoS &D, const HoS &P) {
-    auto area = [](const HoS &a, const HoS &b, const HoS &c) { return (b.x - a.x) * (c.y - a.y) - (b.y - a.y) * (c.x - a.x); };
-    const double aTDO = area(T, D, O);
-    double val = T.n * area(D, P, O);
-    val -= D.n * area(T, P, O);
-    val += P.n * aTDO;
-    val -= O.n * area(T, D, P);
-    return (aTDO > 0) & (val < -(FLT_EPSILON * 0.125));
-}
-}  // namespace
+// ---- hand-over: the previous insert's star walked through its arrays (subdiv2d.h) ----
+#if defined(__x86_64__)
+#ifndef AOS_HO_VEC
+#define AOS_HO_VEC 1   // 0: every hand-over test and copy one slot at a time (the A/B of DESIGN.md 6.1)
+#endif
+
 
 // Walk of the three roots when p lies in the fan triangle (x_k, x_k-1, c) of the previous star O (subdiv2d.h): the
 // roots are L_k (link), S_k-1 (descending chain) and Sym S_k (ascending chain); shift rotates the order
@@ -613,7 +443,7 @@ AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, i
 // link slot j: a leaf is copied from the old ring (its right triangle is untouched), a swap leaves the star
 #define HO_LINK(j, swaps) do { \
         if (swaps) { \
-            q = ho_walk(o.bd[j], Pv, sA, N, q, lf); \
+            q = cavity_walk(o.bd[j], Pv, sA, N, q, lf); \
             if (q < 0) return false; \
             lf = ho_lf; n = ring_ptrs(N); \
         } else { \
@@ -636,7 +466,7 @@ AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, i
         const int kind = (r + shift) % 3;   // 0 ascending, 1 descending, 2 link
         if (kind == 2) {
             SDP_INC(dfs_steps);
-            const bool f = ho_test1(HO_AS(k), HO_XS(k), HO_XS(k - 1), Ps);
+            const bool f = flips(HO_AS(k), HO_XS(k), HO_XS(k - 1), Ps);
             HO_LINK(k, f);
         } else if (kind == 1) {
             // S_j = x_j -> c for j = k - 1, k - 2, ...: T = x_j-1, O = x_j, D = c; a swap stacks L_j and goes on to S_j-1
@@ -659,7 +489,7 @@ AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, i
                 }
                 SDP_INC(dfs_steps);
                 const int jm = j ? j - 1 : m - 1;
-                if (!ho_test1(HO_XS(jm), HO_XS(j), Cs, Ps)) break;
+                if (!flips(HO_XS(jm), HO_XS(j), Cs, Ps)) break;
                 HO_SWAP(o.bu[jm], o.sp[j]);
                 ++nsw;
                 j = jm;
@@ -689,7 +519,7 @@ AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, i
                     if (i == m) i = 0;
                 } else {
                     SDP_INC(dfs_steps);
-                    const bool f = ho_test1(HO_AS(i), HO_XS(i), HO_XS(i - 1), Ps);
+                    const bool f = flips(HO_AS(i), HO_XS(i), HO_XS(i - 1), Ps);
                     HO_LINK(i, f);
                     i = i + 1 == m ? 0 : i + 1; --cnt;
                 }
@@ -727,10 +557,10 @@ AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, i
                 }
                 SDP_INC(dfs_steps);
                 const int jn = j + 1 == m ? 0 : j + 1;
-                if (!ho_test1(HO_XS(jn), Cs, HO_XS(j), Ps)) break;
+                if (!flips(HO_XS(jn), Cs, HO_XS(j), Ps)) break;
                 HO_SWAP(o.bu[jn], o.sp[j] ^ 2);
                 SDP_INC(dfs_steps);
-                const bool f = ho_test1(HO_AS(jn), HO_XS(jn), HO_XS(j), Ps);
+                const bool f = flips(HO_AS(jn), HO_XS(jn), HO_XS(j), Ps);
                 HO_LINK(jn, f);
                 j = jn;
             }
@@ -752,22 +582,27 @@ AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, i
     q_out = q;
     return true;
 }
+#endif   // __x86_64__
 
 AOS_AVX2 static int find_int(const int *a, int m, int v) {   // the first i < m with a[i] == v, or -1
-    const __m256i V = _mm256_set1_epi32(v);
     int i = 0;
+#if defined(__x86_64__)
+    const __m256i V = _mm256_set1_epi32(v);
     for (; i + 8 <= m; i += 8) {
         const int mask = _mm256_movemask_ps(_mm256_castsi256_ps(_mm256_cmpeq_epi32(_mm256_loadu_si256((const __m256i *)(a + i)), V)));
         if (mask) return i + __builtin_ctz(mask);
     }
+#endif
     for (; i < m; ++i) if (a[i] == v) return i;
     return -1;
 }
 
-// insert_cavity with the hand-over: the same walk, started either through the previous star's arrays (ho_fast) or,
-// when p does not lie in a fan triangle of the previous insert, from the three roots by ho_walk; both leave the new
-// star's ring in the other buffer.
-bool Subdiv2D::insert_cavity_ho(int e0, int p) {
+// Cavity form of an INSIDE insert (subdiv2d.h). e0 = locate's edge: p lies left of it, inside the triangle (e0,
+// Lnext e0, Lnext^2 e0). The walk starts either through the previous star's arrays (ho_fast, with the hand-over on)
+// or, when p does not lie in a fan triangle of the previous insert, from the three roots by cavity_walk; both leave
+// the new star's ring in the other buffer. Returns false, with nothing of the new star in the records, when the walk meets an apex that
+// is already a cavity vertex; the caller then runs the connects and the swap loop.
+bool Subdiv2D::insert_cavity(int e0, int p) {
     if (++stamp >= (1 << 29)) {
         flush();   // (the pocket test needs the pending ring's stamps)
         for (V2d &x : vd) x.stamp = 0;
@@ -824,6 +659,7 @@ bool Subdiv2D::insert_cavity_ho(int e0, int p) {
             fast = (unsigned)k < (unsigned)O.m && o.bd[k] == L && (o.sp[k] ^ 2) == asc && o.sp[k - 1] == desc;
         }
     }
+#if defined(__x86_64__)
     if (fast) {
         last_ho_slot = k; last_ho_ring = O.m;
         ho_hz = pending ? ho_stamp : -1;
@@ -835,11 +671,13 @@ bool Subdiv2D::insert_cavity_ho(int e0, int p) {
             return false;
         }
         lf = ho_lf;
-    } else {
+    } else
+#endif
+    {
         flush();
         ho_hz = -1;
-        if ((q = ho_walk(eA, P, sA, N, 0, -1)) < 0 || (q = ho_walk(eB, P, sA, N, q, ho_lf)) < 0 ||
-            (q = ho_walk(e0, P, sA, N, q, ho_lf)) < 0) {
+        if ((q = cavity_walk(eA, P, sA, N, 0, -1)) < 0 || (q = cavity_walk(eB, P, sA, N, q, ho_lf)) < 0 ||
+            (q = cavity_walk(e0, P, sA, N, q, ho_lf)) < 0) {
             ho_valid = false;
             return false;
         }
@@ -853,14 +691,18 @@ bool Subdiv2D::insert_cavity_ho(int e0, int p) {
     n.bd[m] = n.bd[0]; n.bu[m] = n.bu[0]; n.sp[m] = n.sp[0]; n.x[m] = n.x[0]; n.y[m] = n.y[0]; n.n[m] = n.n[0];
     n.bd[-1] = n.bd[m - 1]; n.bu[-1] = n.bu[m - 1]; n.sp[-1] = n.sp[m - 1];
     n.x[-1] = n.x[m - 1]; n.y[-1] = n.y[m - 1]; n.n[-1] = n.n[m - 1];
-    const int c0 = new_edge(), c1 = new_edge(), c2 = new_edge();   // first -> p, v1 -> p, v2 -> p (= cn[0 .. 2])
+    // The outcome. OpenCV's two connectEdges (after the first newEdge + splice) number the three new quad-edges
+    // first -> p, v1 -> p, v2 -> p in that order; everything else they write (the rings of first, v1, v2 and p next to
+    // the new edges, their end points, firstEdge) is rewritten by the ring pass, which sets every field of every spoke
+    // and the ring links of the boundary edges on both sides of it. So only their allocations are kept.
+    const int c0 = new_edge(), c1 = new_edge(), c2 = new_edge();   // (= cn[0 .. 2])
     (void)c0; (void)c1;
     vfirst[p] = sym(lf >= 0 ? lf : c2);   // the last setEdgePoints with p as destination
     if (pending) retire(O, ho_jA, ho_jD);   // (fast: what survives of the old star; the rest is N's to write)
-    ho_cur ^= 1; ho_c = p; ho_valid = true; ho_stamp = sA;
+    ho_cur ^= 1; ho_c = p; ho_valid = use_ho; ho_stamp = sA;
     n_handover += fast;
     pending = false;
-    if (use_def) {
+    if (use_ho & use_def) {   // (a star is left pending only where the next insert can walk it)
         // recentEdge = e0 in the new ring: the last leaf if its test did not swap, else the spoke of its apex
         int s = m - 1, kind = 0;
         if (n.bd[s] != e0) { kind = 2; s = find_int(n.sp, m, e0); }
@@ -872,7 +714,9 @@ bool Subdiv2D::insert_cavity_ho(int e0, int p) {
 #endif
         }
     }
-    if (!pending) ring_pass_ho(ri(), vfirst.data(), n.bd, n.bu, n.sp, m, p);
+    static_assert(sizeof(Rec) == 32 && sizeof(Half) == 16 && offsetof(Half, op) == 4 && offsetof(Half, org) == 8 &&
+                  offsetof(Half, x) == 12, "slot_fields: Rec layout");
+    if (!pending) ring_pass(ri(), vfirst.data(), n.bd, n.bu, n.sp, m, p);
     SDP_ADD(t_write, t_wr);
     return true;
 }
@@ -883,7 +727,7 @@ void Subdiv2D::flush() {
     SDP_T0(t_wr);
     Ring &R = ho[ho_cur];
     const RingP r = ring_ptrs(R);
-    ring_pass_ho(ri(), vfirst.data(), r.bd, r.bu, r.sp, R.m, ho_c);
+    ring_pass(ri(), vfirst.data(), r.bd, r.bu, r.sp, R.m, ho_c);
     pending = false;
     SDP_ADD(t_write, t_wr);
 }
@@ -901,28 +745,18 @@ void Subdiv2D::retire(Ring &O, int jA, int jD) {
     g_sdprof.kept_slots += (jD - jA + m) % m + 1;
 #endif
     for (int j = jA;; j = j + 1 == m ? 0 : j + 1) {
-        const int L = o.bd[j], sLn = o.bd[j + 1] ^ 2, S = o.sp[j], sS = S ^ 2;
-        R[2 * (ptrdiff_t)L] = S;
-        R[2 * (ptrdiff_t)L + 3] = j;
-        R[2 * (ptrdiff_t)sLn + 1] = S;
-        int *a = R + 2 * (ptrdiff_t)S, *b = R + 2 * (ptrdiff_t)sS;
-        a[0] = sLn; a[1] = L; a[2] = o.bu[j];
-        b[0] = o.sp[j - 1] ^ 2; b[1] = o.sp[j + 1] ^ 2; b[2] = c;
-        vfirst[o.bu[j]] = S;
+        slot_write(R, vfirst.data(), j, o.bd[j], o.bd[j + 1], o.bu[j], o.sp[j - 1], o.sp[j], o.sp[j + 1], c);
         if (j == jD) break;
     }
 }
 
+// f(int &field) over every pending field of ho[ho_cur] (the checkers' poison, and same_state's save and restore)
 template <class Fn> void Subdiv2D::for_pending(Fn f) {
     Ring &Rg = ho[ho_cur];
     const RingP r = ring_ptrs(Rg);
-    int *const R = ri();
-    for (int k = 0; k < Rg.m; ++k) {
-        const int L = r.bd[k], sLn = r.bd[k + 1] ^ 2, S = r.sp[k], sS = S ^ 2;
-        f(R[2 * (ptrdiff_t)L]); f(R[2 * (ptrdiff_t)L + 3]); f(R[2 * (ptrdiff_t)sLn + 1]);
-        for (int i = 0; i < 3; ++i) { f(R[2 * (ptrdiff_t)S + i]); f(R[2 * (ptrdiff_t)sS + i]); }
-        f(vfirst[r.bu[k]]);
-    }
+    for (int k = 0; k < Rg.m; ++k)
+        slot_fields(ri(), vfirst.data(), k, r.bd[k], r.bd[k + 1], r.bu[k], r.sp[k - 1], r.sp[k], r.sp[k + 1], ho_c,
+                    [&](int &field, int) { f(field); });
 }
 
 // locate()'s loop while it stays inside the pending star of c = ho_c (subdiv2d.h): the current edge is (kind, slot) of
@@ -992,12 +826,6 @@ bool Subdiv2D::locate_star(float px, float py, int &out_edge) {
     SDP_ADD(t_locate, t_loc);
     return found;
 }
-#else
-bool Subdiv2D::insert_cavity_ho(int e0, int p) { return insert_cavity<false>(e0, p); }
-void Subdiv2D::flush() {}
-bool Subdiv2D::locate_star(float, float, int &) { return false; }
-template <class Fn> void Subdiv2D::for_pending(Fn) {}
-#endif
 
 // Compared through a flushed view: a pending star's fields are saved, the pass is run, and after the comparison the
 // fields are put back, so that the live instance stays exactly as deferred as it was.
@@ -1067,6 +895,7 @@ static void export_recs_scalar(const int *R, int *out, int q0, int q1) {
         std::memcpy(out + 8 * (size_t)q, o, sizeof(o));
     }
 }
+#if defined(__x86_64__)
 AOS_AVX2 static void export_recs_avx2(const int *R, int *out, int q0, int q1) {
     if (q0 == 0 && q1 > 0) { export_recs_scalar(R, out, 0, 1); q0 = 1; }
     const __m256i perm = _mm256_setr_epi32(0, 1, 4, 5, 2, 0, 6, 0);   // on0 op0 on1 op1 org0 . org1 .
@@ -1082,6 +911,9 @@ AOS_AVX2 static void export_recs_avx2(const int *R, int *out, int q0, int q1) {
         _mm256_storeu_si256(reinterpret_cast<__m256i *>(out + 8 * (size_t)q), o);
     }
 }
+#else
+static void export_recs_avx2(const int *R, int *out, int q0, int q1) { export_recs_scalar(R, out, q0, q1); }   // (simd_ok() is false)
+#endif
 
 Subdiv2D::Raw Subdiv2D::raw_into(void *dst, int chunk_recs, const std::function<void(size_t, size_t)> &written) const {
     const_cast<Subdiv2D *>(this)->flush();   // (pending state is not observable: the export sees the written star)

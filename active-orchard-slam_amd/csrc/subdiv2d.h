@@ -20,7 +20,7 @@
 // an insert performs ~56 swaps (~115 flip-loop steps) as each new seed on the next tree line takes
 // over the fan of the previous one, so these constant factors are the replay's cost.
 //
-// Cavity form of the swap loop (insert_cavity). Every triangle the swap loop tests lies across a
+// Cavity form of the swap loop (insert_cavity, cavity_walk). Every triangle the swap loop tests lies across a
 // link edge from the new point p, so it is never incident to p: it is an *old* triangle, untouched
 // when it is tested. Each test is therefore a pure function of the triangulation before the insert,
 // and the loop is a depth-first pre-order walk of the cavity tree (children in clockwise order
@@ -33,23 +33,28 @@
 //     (link) edges fixes; the unique onext/oprev values are stored directly.
 // The swap loop stays as the reference path (on-edge inserts, and any walk that meets an apex that is
 // already a cavity vertex). tools/sdcheck compares the two paths' complete state after every insert.
-//
-// Hand-over (insert_cavity_ho, on by default where the CPU has AVX2). On seed rows nearly every point lands in a
-// fan triangle of the previous insert's star, and nearly all of the walk's tests lie in that star or on its ring.
-// Each cavity insert therefore leaves its ring behind as arrays (struct Ring: per slot k in walk order the link
-// edge L_k = x_k -> x_k-1, its origin, the apex of its untouched right triangle, the spoke S_k = x_k -> centre, and
-// the double coordinates and |.|^2 of x_k and of the apex, padded cyclically), and the next insert walks the star
-// through them: the same tests with the same operands in the same order, four slots at a time, without following
-// oprev / dst / vertex loads, and the new ring is copied from the old one in runs. A spoke's ring links (ring_pass):
+// There is one form of each part: the flip test (flips(), and ho_test4 whose lanes are that function), the walk
+// (cavity_walk, from a link edge, reading the records), and the write (ring_pass over slot_fields()). The walk
+// leaves the boundary (link) edges in walk order as a ring in arrays (struct Ring: per slot k the link edge
+// L_k = x_k -> x_k-1, its origin, the apex of its untouched right triangle, the spoke S_k = x_k -> centre, and the
+// double coordinates and |.|^2 of x_k and of the apex, padded cyclically), and ring_pass writes the star from them:
 //   Oprev(S_j) = L_j,  Oprev(Sym S_j) = Sym S_j+1,  Sym Onext(Sym S_j) = S_j-1,  Sym Onext(S_j) = L_j+1.
-// A link edge that swaps leaves the star: the generic walk runs from it. All of this state is per instance.
+//
+// Hand-over (ho_fast, on by default where the CPU has AVX2; set_handover). On seed rows nearly every point lands in
+// a fan triangle of the previous insert's star, and nearly all of the walk's tests lie in that star or on its ring.
+// The ring a cavity insert left behind stays valid for the next one (two buffers alternate), and the next insert
+// walks the star through it: the same tests with the same operands in the same order, four slots at a time, without
+// following oprev / dst / vertex loads, and the new ring is copied from the old one in runs. A link edge that swaps
+// leaves the star: cavity_walk runs from it. With the hand-over off, or where the new point does not lie in the
+// previous star, cavity_walk runs from the three roots. All of this state is per instance.
 //
 // Deferred star (set_deferred, on by default with the hand-over). The next insert's pass rewrites about nine tenths of
 // what ring_pass writes (on seed rows a ring of 60 slots keeps 4-5 of its spokes), and between two inserts only
-// locate() reads records, nearly always inside that star. So a hand-over insert does not run its ring pass: the star
-// stays *pending*, described by the ring arrays alone. Pending are exactly the fields ring_pass writes: per slot k
-// Onext(L_k), Oprev(Sym L_k+1), the slot int of L_k, every field of S_k and Sym S_k, and firstEdge of x_k. All that
-// faces outward from the ring (Oprev(L_k), Onext(Sym L_k), the link edges' end points) is valid in the records.
+// locate() reads records, nearly always inside that star. So with the hand-over on a cavity insert does not run its
+// ring pass: the star stays *pending*, described by the ring arrays alone (never with the hand-over off). Pending are
+// exactly the fields ring_pass writes, which slot_fields() names: per slot k Onext(L_k), Oprev(Sym L_k+1), the slot
+// int of L_k, every field of S_k and Sym S_k, and firstEdge of x_k. All that faces outward from the ring
+// (Oprev(L_k), Onext(Sym L_k), the link edges' end points) is valid in the records.
 //   * locate() walks its loop on the arrays while it stays in the star (locate_star: same predicate arithmetic and
 //     branch order; transitions Onext L_s = S_s, Dprev L_s = Sym S_s-1, Dprev S_s = S_s+1, Onext Sym S_s = Sym S_s-1;
 //     Onext S_s and Dprev Sym S_s are Sym L, which leaves the star). Any zero predicate, a step out of the star, or a
@@ -95,10 +100,11 @@ class Subdiv2D {
     bool insert(float x, float y);
     // 0: cavity DFS + bulk write (default); 1: always OpenCV's swap loop (reference / cross-check)
     void set_swap_loop(bool on) { flush(); force_loop = on; }
-    void set_simd(bool on) { flush(); use_avx2 = on && simd_ok(); }   // batched boundary flip tests on AVX2 (off by default)
-    // walk the previous insert's star through the arrays it left (see above); needs AVX2, else the generic walk runs
+    // walk the previous insert's star through the arrays it left (see above); needs AVX2. Off: every cavity insert
+    // walks from its three roots (n_handover stays 0) and no star is left pending
     void set_handover(bool on) { flush(); use_ho = on && simd_ok(); ho_valid = false; }
-    // leave a hand-over insert's star pending in the ring arrays (see above); off: every insert runs its ring pass
+    // leave a cavity insert's star pending in the ring arrays (see above; only with the hand-over on); off: every
+    // insert runs its ring pass
     void set_deferred(bool on) { flush(); use_def = on; }
     void flush();                    // writes a pending star into the records (no-op without one)
     bool star_pending() const { return pending; }
@@ -154,12 +160,12 @@ class Subdiv2D {
     std::vector<int> vfirst, vtype;   // type: -1 free, 0 real, 1 virtual
     std::vector<int> qx;              // export buffer (Raw::qe)
     int free_q = 0, free_p = 0, recent = 0;
-    bool force_loop = false, use_avx2 = false;
-    // cavity DFS scratch: stack of link edges, boundary edges in walk order (with their origins); per
-    // vertex (V2d) the spoke, valid while its stamp is this insert's
-    std::vector<int> dfs_stack, cav_bnd, cav_bu;
+    bool force_loop = false;
+    // cavity walk scratch: stack of link edges; per vertex (V2d) the spoke, valid while its stamp is this insert's
+    std::vector<int> dfs_stack;
     int stamp = 0;
-    // hand-over state: two ring buffers that alternate (ho[ho_cur] describes the star of vertex ho_c while ho_valid)
+    // the walk's output, and the hand-over's input: two ring buffers that alternate (ho[ho_cur] describes the star of
+    // vertex ho_c while ho_valid)
     struct Ring {
         std::vector<int> bd, bu, ba, sp;
         std::vector<double> x, y, n, ax, ay, an;
@@ -173,7 +179,7 @@ class Subdiv2D {
     bool pending = false, use_def = true, ho_pocket = false;
     int rs_kind = 0, rs_slot = 0;    // kind: 0 L_s, 2 S_s, 3 Sym S_s
     int loc_k = -1, loc_shift = 0;   // set by locate_star (loc_k < 0: the generic locate ran)
-    int ho_stamp = -1, ho_hz = -1;   // the pending ring's vertex stamp; the stamp ho_walk treats as a pocket (-1: none)
+    int ho_stamp = -1, ho_hz = -1;   // the pending ring's vertex stamp; the stamp cavity_walk treats as a pocket (-1: none)
     int ho_jA = 0, ho_jD = 0;        // ho_fast: the slots where the ascending and descending chains ended
     float tlx = 0, tly = 0, brx = 0, bry = 0;
 
@@ -214,14 +220,11 @@ class Subdiv2D {
     template <class F> void for_pending(F f);   // f(int &field) over every pending field of ho[ho_cur]
     bool same_records(const Subdiv2D &o) const;
     void swap_loop(int curr_edge, int first_point, int curr_point);
-    void flip_tests_scalar(const int *es, int n, const V2d &P, int *out) const;
-    void flip_tests_avx2(const int *es, int n, const V2d &P, int *out) const;
-    template <bool SIMD> bool insert_cavity(int e0, int curr_point);
     static RingP ring_ptrs(Ring &r);
     static void ring_reserve(Ring &r, int slots);
-    bool insert_cavity_ho(int e0, int curr_point);
-    int ho_walk(int e, const V2d &P, int sA, Ring &N, int q, int last_flip);
-    bool ho_fast(Ring &O, Ring &N, int k, int shift, int p, int c, int sA, int &q_out);
+    bool insert_cavity(int e0, int curr_point);
+    int cavity_walk(int e, const V2d &P, int sA, Ring &N, int q, int last_flip);
+    bool ho_fast(Ring &O, Ring &N, int k, int shift, int p, int c, int sA, int &q_out);   // (x86-64 only)
     void calc_voronoi();   // calcVoronoi on the exported layout (qx), creating the virtual vertices
     int facet_next(int e) const;
 };

@@ -15,13 +15,16 @@ SRC = os.path.join(ROOT, "active-orchard-slam_amd", "csrc", "subdiv2d.cpp")
 
 SHIM = r"""
 #include "subdiv2d.h"
+enum { NST = 16 };   // counters per instance
 // stats: inserts that returned true, n_handover, n_cavity, n_loop, n_ho_bail, hand-over inserts whose located fan
-// triangle sat at ring slot 0, and at slot m - 1
+// triangle sat at ring slot 0, and at slot m - 1, n_deferred, inserts after which a star was pending
 static void count(const aos::Subdiv2D& a, bool ok, long* st) {
     st[0] += ok;
     st[1] = a.n_handover; st[2] = a.n_cavity; st[3] = a.n_loop; st[4] = a.n_ho_bail;
     if (a.last_ho_slot == 0) st[5]++;
     if (a.last_ho_slot >= 0 && a.last_ho_slot == a.last_ho_ring - 1) st[6]++;
+    st[7] = a.n_deferred;
+    st[8] += a.star_pending();
 }
 // returns -1 when the states were equal after every insert, else the index of the first insert after which they differ
 extern "C" int ho_check(const double* s, int n, float rx, float ry, float rw, float rh, int handover, long* st) {
@@ -29,7 +32,7 @@ extern "C" int ho_check(const double* s, int n, float rx, float ry, float rw, fl
     a.set_handover(handover != 0);
     r.set_swap_loop(true);
     a.init_delaunay(rx, ry, rw, rh, 0); r.init_delaunay(rx, ry, rw, rh, 0);
-    for (int i = 0; i < 8; ++i) st[i] = 0;
+    for (int i = 0; i < NST; ++i) st[i] = 0;
     for (int i = 0; i < n; ++i) {
         const bool ka = a.insert((float)s[2 * i], (float)s[2 * i + 1]), kr = r.insert((float)s[2 * i], (float)s[2 * i + 1]);
         if (ka != kr || !a.same_state(r)) return i;
@@ -46,14 +49,14 @@ extern "C" int ho_check2(const double* s1, int n1, const double* s2, int n2, flo
         r[k].set_swap_loop(true);
         a[k].init_delaunay(rx, ry, rw, rh, 0); r[k].init_delaunay(rx, ry, rw, rh, 0);
     }
-    for (int i = 0; i < 16; ++i) st[i] = 0;
+    for (int i = 0; i < 2 * NST; ++i) st[i] = 0;
     for (int i = 0; i < n1 || i < n2; ++i)
         for (int k = 0; k < 2; ++k) {
             if (i >= n[k]) continue;
             const float x = (float)s[k][2 * i], y = (float)s[k][2 * i + 1];
             const bool ka = a[k].insert(x, y), kr = r[k].insert(x, y);
             if (ka != kr || !a[k].same_state(r[k])) return 2 * i + k;
-            count(a[k], ka, st + 8 * k);
+            count(a[k], ka, st + NST * k);
         }
     return -1;
 }
@@ -84,13 +87,14 @@ def shim():
 
 RECT = (-5.0, -5.0, 60.0, 40.0)   # x, y, w, h: every row set below lies inside it
 
-STAT = ("inserted", "n_handover", "n_cavity", "n_loop", "n_ho_bail", "seam_first", "seam_last")
+NST = 16   # counters per instance (the shim's NST)
+STAT = ("inserted", "n_handover", "n_cavity", "n_loop", "n_ho_bail", "seam_first", "seam_last", "n_deferred", "pending_after")
 
 
 def check(pts, handover=1):
     """Runs pts through a hand-over instance and a swap-loop instance; returns the hand-over instance's counters."""
     s = np.ascontiguousarray(pts, np.float64).reshape(-1)
-    st = np.zeros(8, np.int64)
+    st = np.zeros(NST, np.int64)
     bad = shim().ho_check(s.ctypes.data, s.size // 2, *RECT, handover, st.ctypes.data)
     assert bad == -1, f"state differs from the swap loop's after insert {bad} of {s.size // 2}"
     return dict(zip(STAT, (int(v) for v in st)))
@@ -119,6 +123,8 @@ def test_rows_equal_swap_loop(n_rows, n, order):
     assert st["n_handover"] > 0
     off = check(rows(n_rows, n, order), handover=0)
     assert off["n_handover"] == 0 and off["inserted"] == n_rows * n
+    # with the hand-over off no star is ever left pending: every insert runs its ring pass
+    assert off["pending_after"] == 0 and off["n_deferred"] == 0
 
 
 @pytest.mark.parametrize("order", [0, 1, 2])
@@ -186,11 +192,11 @@ def test_two_instances_fed_alternately():
     a, b = rows(3, 40, 2, seed=1), rows(5, 13, 1, seed=2, dx=0.7, dy=1.9) + np.array([3.0, 1.0])
     s1 = np.ascontiguousarray(a, np.float64).reshape(-1)
     s2 = np.ascontiguousarray(b, np.float64).reshape(-1)
-    st = np.zeros(16, np.int64)
+    st = np.zeros(2 * NST, np.int64)
     bad = shim().ho_check2(s1.ctypes.data, len(a), s2.ctypes.data, len(b), *RECT, st.ctypes.data)
     assert bad == -1, f"state differs after alternating insert {bad}"
-    assert st[0] == len(a) and st[8] == len(b)
-    assert st[1] > 0.8 * len(a) and st[9] > 0.5 * len(b)
+    assert st[0] == len(a) and st[NST] == len(b)
+    assert st[1] > 0.8 * len(a) and st[NST + 1] > 0.5 * len(b)
 
 
 @pytest.mark.parametrize("order", [0, 1, 2])

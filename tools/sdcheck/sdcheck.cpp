@@ -28,11 +28,10 @@ static double uni() { return (splitmix() >> 11) * (1.0 / 9007199254740992.0); }
 
 struct Case { const char *name; std::vector<double> s; double b[4]; };
 
-static bool check(const Case &c, bool verbose, bool simd, bool handover, bool deferred, bool every) {
+static bool check(const Case &c, bool verbose, bool handover, bool deferred, bool every) {
     float rx = (float)(c.b[0] - 1.0), ry = (float)(c.b[2] - 1.0);
     float rw = (float)(std::abs(c.b[1] - c.b[0]) + 2.0), rh = (float)(std::abs(c.b[3] - c.b[2]) + 2.0);
     aos::Subdiv2D a, r;
-    a.set_simd(simd);
     a.set_handover(handover);
     a.set_deferred(deferred);
     r.set_swap_loop(true);
@@ -68,7 +67,7 @@ static bool check(const Case &c, bool verbose, bool simd, bool handover, bool de
     return true;
 }
 
-static double time_inserts(const Case &c, bool loop, bool simd, bool handover, bool deferred, uint64_t &hash) {
+static double time_inserts(const Case &c, bool loop, bool handover, bool deferred, uint64_t &hash) {
     float rx = (float)(c.b[0] - 1.0), ry = (float)(c.b[2] - 1.0);
     float rw = (float)(std::abs(c.b[1] - c.b[0]) + 2.0), rh = (float)(std::abs(c.b[3] - c.b[2]) + 2.0);
     const int n = (int)c.s.size() / 2;
@@ -76,7 +75,6 @@ static double time_inserts(const Case &c, bool loop, bool simd, bool handover, b
     for (int rep = 0; rep < 7; ++rep) {
         aos::Subdiv2D sd;
         sd.set_swap_loop(loop);
-        sd.set_simd(simd);
         sd.set_handover(handover);
         sd.set_deferred(deferred);
         sd.reserve(n);
@@ -154,27 +152,24 @@ int main(int argc, char **argv) {
         cases.push_back(file);
     }
     int fails = 0;
-    const bool simd = aos::Subdiv2D::simd_ok();
     // legs: the hand-over with the deferred star (the default path; it needs AVX2) compared after every insert and
-    // only at the end, the hand-over with a ring pass per insert, then the generic cavity walk with the batched AVX2
-    // flip tests and with the scalar ones; each against a swap-loop instance fed in step with it.
-    static const char *const leg[5] = {"hand-over on, star deferred", "hand-over on, star deferred, compared at the end only",
-                                       "hand-over on, ring pass per insert", "hand-over off, AVX2 flip tests",
-                                       "hand-over off, scalar flip tests"};
-    for (int pass = simd ? 0 : 4; pass < 5; ++pass) {
+    // only at the end, the hand-over with a ring pass per insert, then the hand-over off (the cavity walk from the
+    // three roots of every insert); each against a swap-loop instance fed in step with it.
+    static const char *const leg[4] = {"hand-over on, star deferred", "hand-over on, star deferred, compared at the end only",
+                                       "hand-over on, ring pass per insert", "hand-over off"};
+    for (int pass = aos::Subdiv2D::simd_ok() ? 0 : 3; pass < 4; ++pass) {
         for (size_t i = 0; i < cases.size(); ++i)
-            fails += !check(cases[i], pass == 0 && (i < 6 || i + 1 == cases.size()), pass == 3, pass <= 2, pass <= 1, pass != 1);
+            fails += !check(cases[i], pass == 0 && (i < 6 || i + 1 == cases.size()), pass <= 2, pass <= 1, pass != 1);
         printf("%zu cases (%s), %d failed so far\n", cases.size(), leg[pass], fails);
     }
     if (path) {
-        uint64_t hd = 0, hh = 0, ha = 0, hs = 0, hr = 0;
-        const double td = time_inserts(file, false, false, true, true, hd), th = time_inserts(file, false, false, true, false, hh),
-                     ta = time_inserts(file, false, simd, false, false, ha), ts = time_inserts(file, false, false, false, false, hs),
-                     tr = time_inserts(file, true, false, false, false, hr);
-        const bool eq = hd == hr && hh == hr && ha == hr && hs == hr;
-        printf("%s inserts: deferred %.2f ms, hand-over %.2f ms, cavity+%s %.2f ms, cavity+scalar %.2f ms, swap loop %.2f ms (x%.2f); "
+        uint64_t hd = 0, hh = 0, hs = 0, hr = 0;
+        const double td = time_inserts(file, false, true, true, hd), th = time_inserts(file, false, true, false, hh),
+                     ts = time_inserts(file, false, false, false, hs), tr = time_inserts(file, true, false, false, hr);
+        const bool eq = hd == hr && hh == hr && hs == hr;
+        printf("%s inserts: deferred %.2f ms, hand-over %.2f ms, hand-over off %.2f ms, swap loop %.2f ms (x%.2f); "
                "facet-edge hash %016llx %s\n",
-               path, td, th, simd ? "AVX2" : "scalar", ta, ts, tr, tr / td, (unsigned long long)hd, eq ? "equal" : "DIFFERENT");
+               path, td, th, ts, tr, tr / td, (unsigned long long)hd, eq ? "equal" : "DIFFERENT");
         if (!eq) fails++;
     }
     return fails ? 1 : 0;

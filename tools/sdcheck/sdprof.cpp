@@ -30,7 +30,7 @@ int main(int argc, char **argv) {
     uint64_t hash = 0;
     long n_cavity = 0, n_handover = 0, n_ho_bail = 0, n_loop = 0, n_deferred = 0, n_ho_pocket = 0;
 #ifdef AOS_SD_HANDOVER   // (a variant built against an older subdiv2d.h has no hand-over)
-    const bool handover = !getenv("AOS_SD_NO_HANDOVER");   // (set: the generic cavity walk only)
+    const bool handover = !getenv("AOS_SD_NO_HANDOVER");   // (set: cavity_walk from every insert's three roots, a ring pass per insert)
 #endif
 #ifdef AOS_SD_DEFERRED   // (likewise: an older subdiv2d.h has no deferred star)
     const bool deferred = !getenv("AOS_SD_NO_DEFERRED");   // (set: a ring pass per insert)
