@@ -272,6 +272,8 @@ def lib():
         L.aos_debug_faults.argtypes = [c_i, c_u64]
         L.aos_debug_replay.restype = None
         L.aos_debug_replay.argtypes = [c_i, c_i, c_i]
+        L.aos_debug_limits.restype = None
+        L.aos_debug_limits.argtypes = [c_i, c_i, c_i]
         L.aos_replay_counts.argtypes = [c_vp, ctypes.POINTER(ctypes.c_int32)]
         L.aos_comm_init.restype = None
         L.aos_comm_init.argtypes = [c_vp]
@@ -622,6 +624,13 @@ def debug_replay(gpu_min_clusters: int = -1, ring_cap: int = 0, replay_all: bool
     its clusters on the GPU (-1: the library default; 0: always), a smaller queue ring for the GPU walk (0: 64),
     and replay_all: every cluster replayed, certified or not. No arguments: the defaults."""
     lib().aos_debug_replay(int(gpu_min_clusters), int(ring_cap), int(bool(replay_all)))
+
+
+def debug_limits(thin_cap: int = -1, ccl_edge_cap: int = -1, stats_lds: int = -1) -> None:
+    """aos_debug_limits (test hook, process-wide): a cap on a frame's thinning launches (at least 1), the capacity
+    of the cluster stage's link list (at least 2), and stats_lds = 0: the cluster statistics read the cluster table
+    from global memory. A negative value restores that default; no arguments: all three defaults."""
+    lib().aos_debug_limits(int(thin_cap), int(ccl_edge_cap), int(stats_lds))
 
 
 class Group:

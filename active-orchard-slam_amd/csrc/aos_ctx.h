@@ -133,22 +133,18 @@ struct aos_ctx {
     // First thinning batch (n temporal-block launches; the opening, which clears the flags, runs just before it so the
     // inflated grid's read-back can be queued behind it) as hipGraphs, one per batch
     // size n (a power of two), captured on first use and replayed while every pointer and size baked into
-    // the graph is unchanged (seedgen.hip thin_first_batch). Graph shape: AOS_THIN_GRAPH (see there).
+    // the graph is unchanged (seedgen.hip thin_first_batch). aos_params.thin_graph = 0: plain launches.
     struct ThinGraph {
         hipGraphExec_t exec = nullptr;
-        std::array<const void *, 8> ptrs{};   // every device / host pointer a node holds
-        std::array<int, 8> dims{};            // W, H, WW, R, launches, flag ints, shape, tiles
+        std::array<const void *, 5> ptrs{};   // every device pointer a node holds
+        std::array<int, 7> dims{};            // W, H, WW, R, launches, flag ints, tiles
     };
     std::vector<ThinGraph> thin_graphs;
-    int thin_graph_shape = -1;                // AOS_THIN_GRAPH at create (default 1)
     int last_thin_graph = 0, last_thin_launches = 0;
-    bool thin_graph_check = false;            // AOS_THIN_GRAPH_CHECK (diagnosis)
-    long thin_checks = 0, thin_check_failures = 0;
     void thin_graphs_release();
-    bool thin_first_batch(const aos::FrameGeom &g, const uint64_t *d_ibits, uint64_t *d_open, uint64_t *const bufs[2],
-                          int *d_flags, int *h_flags, int *d_act, int nflags, int &batch_n, int cap_launches,
+    void thin_first_batch(const aos::FrameGeom &g, const uint64_t *d_ibits, uint64_t *d_open, uint64_t *const bufs[2],
+                          int *d_flags, int *d_act, int nflags, int &batch_n, int cap_launches,
                           const std::function<void(int)> &launch_next, const std::function<void()> &after_open);
-    void thin_check_flags(const int *d_flags, const int *h_flags, int n_read, int nflags);
     uint64_t n_ror_kept = 0, n_clipped = 0;
     double ror_est_binned = 0;             // binned points of the last frame (sizes the ROR tiles)
     double ror_staged_max = 0;             // largest staged (own + halo) count seen (sizes the scatter)

@@ -222,7 +222,6 @@ void launch_thin_block(const uint64_t *in, uint64_t *out, const FrameGeom &g, in
 // (h_flags: pinned, receives flags[0, nh) in the same launch)
 void launch_thin_pick(const int *flags, int launched, const uint64_t *b0, const uint64_t *b1, uint64_t *out, size_t n,
                       hipStream_t s, int *h_flags = nullptr, int nh = 0);
-void launch_zero_ints(int *p, int n, hipStream_t s);   // a kernel (no memset node in a captured graph)
 
 // ------------------------------------------------------------------ frame helpers (seedgen.hip)
 FrameGeom frame_geom(const Poly &poly, const aos_params &P);
@@ -236,6 +235,10 @@ struct CommError { std::string what; };
 // cluster exchange's round-size cap in bytes (0: none)
 extern std::atomic<int> g_debug_stuck_rank;
 extern std::atomic<uint64_t> g_debug_a2a_round;
+// aos_debug_limits (test hooks; -1: the default): the cap on a frame's thinning launches (seedgen.hip), the
+// cluster stage's link-list capacity and whether its statistics kernel copies the cluster table into LDS
+// (cluster_seed.hip)
+extern std::atomic<int> g_debug_thin_cap, g_debug_ccl_ecap, g_debug_stats_lds;
 // RCCL communicator (rccl_comm.hip; aos_rccl_* in the ABI)
 void rccl_unique_id(uint8_t *id);
 aos_rccl *rccl_create(const uint8_t *id, int rank, int world, int device, uint64_t buf_bytes);

@@ -60,6 +60,9 @@ std::atomic<uint64_t> g_debug_a2a_round{0};
 std::atomic<int> g_debug_replay_min{-1};
 std::atomic<int> g_debug_replay_ring{0};
 std::atomic<bool> g_debug_replay_all{false};
+std::atomic<int> g_debug_thin_cap{-1};
+std::atomic<int> g_debug_ccl_ecap{-1};
+std::atomic<int> g_debug_stats_lds{-1};
 }  // namespace aos
 
 extern "C" {
@@ -132,6 +135,12 @@ void aos_debug_replay(int32_t gpu_min_clusters, int32_t ring_cap, int32_t replay
     aos::g_debug_replay_all.store(replay_all != 0, std::memory_order_relaxed);
     aos::g_debug_replay_min.store(gpu_min_clusters < 0 ? -1 : gpu_min_clusters, std::memory_order_relaxed);
     aos::g_debug_replay_ring.store(ring_cap > 0 ? ring_cap : 0, std::memory_order_relaxed);
+}
+
+void aos_debug_limits(int32_t thin_cap_launches, int32_t ccl_edge_cap, int32_t stats_lds) {
+    aos::g_debug_thin_cap.store(thin_cap_launches < 0 ? -1 : thin_cap_launches, std::memory_order_relaxed);
+    aos::g_debug_ccl_ecap.store(ccl_edge_cap < 0 ? -1 : ccl_edge_cap, std::memory_order_relaxed);
+    aos::g_debug_stats_lds.store(stats_lds < 0 ? -1 : stats_lds, std::memory_order_relaxed);
 }
 
 int aos_replay_counts(aos_ctx *c, int32_t out[4]) {

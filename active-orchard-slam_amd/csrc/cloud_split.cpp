@@ -120,8 +120,7 @@ __attribute__((target("avx512f,popcnt"))) uint64_t split_avx512(const uint8_t *s
 bool pack_simd() {
     int s = g_simd.load(std::memory_order_relaxed);
     if (s < 0) {
-        const char *e = getenv("AOS_PACK_SIMD");
-        s = (e && atoi(e) == 0) ? 0 : (cpu_avx512() ? 1 : 0);
+        s = cpu_avx512() ? 1 : 0;   // (pack_set_simd(false): the scalar path, for tests)
         g_simd.store(s, std::memory_order_relaxed);
     }
     return s == 1;

@@ -21,8 +21,8 @@ void pack_all(const uint8_t *src, uint64_t m, const PackLayout &l, float *out);
 uint64_t pack_split(const uint8_t *src, uint64_t m, const PackLayout &l, const float box[6], float *front, float *rest,
                     uint64_t *n_rest);
 
-// AVX-512 path for the common 16-byte layout (x, y, z at 0, 4, 8): on where the CPU has AVX-512F and
-// AOS_PACK_SIMD is not 0. pack_set_simd: tests compare both paths.
+// AVX-512 path for the common 16-byte layout (x, y, z at 0, 4, 8): on where the CPU has AVX-512F.
+// pack_set_simd: tests compare both paths.
 bool pack_simd();
 void pack_set_simd(bool on);
 

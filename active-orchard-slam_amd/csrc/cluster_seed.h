@@ -234,12 +234,6 @@ struct alignas(128) CellsWork {
     std::vector<int32_t> cell_off;
     std::vector<float> cell_rgba;
     float ms = 0;
-    // its facets are built on the GPU too, on the worker's own stream
-    int device = 0;
-    hipStream_t stream = nullptr;
-    FacetBufs fb;
-    DevBuf edges;
-    PinnedBuf h;
     // One persistent worker per handle: it sleeps between frames and keeps its core (and the
     // replay's ~6 MB of quad-edges in that core's caches); a thread per frame landed on a cold core.
     std::thread worker;
@@ -257,7 +251,6 @@ struct alignas(128) CellsWork {
             cv.notify_all();
             worker.join();
         }
-        if (stream) (void)hipStreamDestroy(stream);
     }
 };
 

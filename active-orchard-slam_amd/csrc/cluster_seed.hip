@@ -105,16 +105,16 @@ __global__ void k_ccl_union(const int *list, int n, const uint64_t *fg, const in
 // global index of its chunk root; links into an earlier chunk are appended to a cross-edge list that
 // k_ccl_cross then unions globally (C2: ~10^4 edges instead of ~10^6 global unions). The smaller index is
 // always the root, as in k_ccl_union, so the roots and the flattened labels are the same.
-// chunk and block size (AOS_CCL_CHUNK / AOS_CCL_TB override them for A/B runs)
-static int ccl_chunk() { static const int v = [] { const char *e = getenv("AOS_CCL_CHUNK"); return e ? std::max(64, std::min(16384, atoi(e))) : 2048; }(); return v; }
+// chunk and block size, both runtime arguments of the launch (k_ccl_local takes the chunk as a parameter).
 // (1024 threads: k_ccl_local 77 -> 52 us per C2 frame against 256, 60 with 512; 1024-cell chunks 58, 4096 with 1024
-// threads 69: profiles/r05j_ccl_ab.txt)
-static int ccl_tb() { static const int v = [] { const char *e = getenv("AOS_CCL_TB"); return e ? std::max(64, std::min(1024, atoi(e))) / 64 * 64 : 1024; }(); return v; }
-// capacity of k_ccl_local's cross-chunk link list (AOS_DEBUG_CCL_ECAP, read per call: tests force the overflow
-// fallback of k_ccl_cross with a tiny list)
+// threads 69: profiles/r05j_ccl_ab.txt, which was measured with AOS_CCL_CHUNK / AOS_CCL_TB, removed)
+static const int kCclChunk = 2048;
+static const int kCclTB = 1024;
+// capacity of k_ccl_local's cross-chunk link list (aos_debug_limits: tests force the overflow fallback of
+// k_ccl_cross with a tiny list)
 static int ccl_edge_cap(int nf) {
-    const char *e = getenv("AOS_DEBUG_CCL_ECAP");
-    return e ? std::max(2, atoi(e)) : std::max(4096, nf / 4);
+    const int e = g_debug_ccl_ecap.load(std::memory_order_relaxed);
+    return e >= 0 ? std::max(2, e) : std::max(4096, nf / 4);
 }
 constexpr int kCclBatch = 2;        // k_ccl_local: cells per thread whose neighbour lookups are in flight together
 constexpr int kCclEdgeLds = 1024;   // k_ccl_local: cross-chunk links gathered per block before the global append
@@ -555,11 +555,10 @@ __global__ __launch_bounds__(kStatTB) void k_cluster_stats(StatArgs A) {
     }
 }
 
-// clusters read from global memory once when they fit the LDS (AOS_DEBUG_STATS_LDS=0, read per call: every pass
+// clusters read from global memory once when they fit the LDS (aos_debug_limits with stats_lds = 0: every pass
 // from global memory, the path of larger clusters and of grids of 65536 columns or rows and more)
 static int stats_lds_cap(const GridC &g) {
-    const char *e = getenv("AOS_DEBUG_STATS_LDS");
-    if (e && atoi(e) == 0) return 0;
+    if (g_debug_stats_lds.load(std::memory_order_relaxed) == 0) return 0;
     return g.W <= 65536 && g.H <= 65536 ? kStatLds : 0;
 }
 
@@ -778,8 +777,8 @@ int ccl_label(CclScratch &B, const uint64_t *fg, const int *off, const GridC &g,
     int *d_ne = dev<int>(B.edges, 2 + 2 * (size_t)ecap);
     int2 *d_edges = reinterpret_cast<int2 *>(d_ne + 2);
     k_fg_list<<<gw2, 64, 0, s>>>(fg, d_off, B.list_p, g, nullptr, d_ne);
-    const int chunk = ccl_chunk();
-    k_ccl_local<<<cdiv(nf, chunk), ccl_tb(), sizeof(int) * chunk, s>>>(B.list_p, nf, fg, d_off, g, B.parent_p, d_edges, d_ne,
+    const int chunk = kCclChunk;
+    k_ccl_local<<<cdiv(nf, chunk), kCclTB, sizeof(int) * chunk, s>>>(B.list_p, nf, fg, d_off, g, B.parent_p, d_edges, d_ne,
                                                                       ecap - 1, chunk);
     k_ccl_cross<<<256, 256, 0, s>>>(d_edges, d_ne, ecap - 1, B.parent_p, B.list_p, nf, fg, d_off, g);
     ccl_flatten_rank(B.lb, B.parent_p, dev<int>(B.isroot, nf), B.rank_p, nf, s);
@@ -851,8 +850,8 @@ void run_cluster_seed_stage(ClusterSeedState &S, const SeedStageIn &in, SeedStag
         int *d_ne = dev<int>(S.ccl_edges, 2 + 2 * (size_t)ecap);
         int2 *d_edges = reinterpret_cast<int2 *>(d_ne + 2);   // (8-byte aligned: DevBuf bases are)
         k_fg_list<<<gw2, 64, 0, s>>>(d_fg, d_wo, d_list, g, nullptr, d_ne);
-        const int chunk = ccl_chunk();
-        k_ccl_local<<<cdiv(nf, chunk), ccl_tb(), sizeof(int) * chunk, s>>>(d_list, nf, d_fg, d_wo, g, d_par, d_edges, d_ne,
+        const int chunk = kCclChunk;
+        k_ccl_local<<<cdiv(nf, chunk), kCclTB, sizeof(int) * chunk, s>>>(d_list, nf, d_fg, d_wo, g, d_par, d_edges, d_ne,
                                                                           ecap - 1, chunk);
         k_ccl_cross<<<256, 256, 0, s>>>(d_edges, d_ne, ecap - 1, d_par, d_list, nf, d_fg, d_wo, g);
         ccl_flatten_rank(S.lb, d_par, d_isroot, d_rank, nf, s);

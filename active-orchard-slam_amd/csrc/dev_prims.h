@@ -69,13 +69,11 @@ CellIdx cell_index_build(CellScratch &S, const double2 *p, const int *ok, int n,
 // pinned host memory by a kernel instead of hipMemcpyAsync: a D2H copy is queued on the DMA engine behind the
 // frame's 2 x 16.8 MB OccupancyGrid copies (~0.3 ms each at C2), which delayed every host wait of the
 // cluster / seed stage until they had finished. h_dst: pinned host memory (PinnedBuf); the values are the
-// host's once the stream has been synchronised. AOS_ZC_READBACK=0: hipMemcpyAsync instead (A/B).
+// host's once the stream has been synchronised. (hipMemcpyAsync instead was kept for A/B runs as
+// AOS_ZC_READBACK=0, removed.)
 constexpr int kPeekMax = 8;
 void peek_to_host(int *h_dst, std::initializer_list<const int *> srcs, hipStream_t s);
 void copy_to_host(void *h_dst, const void *d_src, size_t bytes, hipStream_t s);
 void copy_from_host(void *d_dst, const void *h_src, size_t bytes, hipStream_t s);   // h_src pinned
-// A bulk copy by a kernel of at most `blocks` workgroups (one side may be pinned host memory): the published
-// grids' D2H (finish_frame), where hipMemcpyAsync now and then held the host for ~3-7 ms (AOS_TRACE)
-void copy_kernel_bulk(void *dst, const void *src, size_t bytes, int blocks, hipStream_t s);
 
 }  // namespace aos

@@ -356,14 +356,6 @@ __global__ __launch_bounds__(kThinTB) void k_thin_block(const uint64_t *__restri
 
 int thin_tiles(const FrameGeom &g) { return cdiv(g.WW, TWW) * cdiv(g.H, TH); }
 
-__global__ void k_zero_ints(int *p, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = 0;
-}
-void launch_zero_ints(int *p, int n, hipStream_t s) {
-    if (n > 0) k_zero_ints<<<cdiv(n, 256), 256, 0, s>>>(p, n);
-}
-
 // The thinning result without a host round trip: the last launch that ran (launch j runs iff j == 0 or
 // iteration j*K-1 deleted something) wrote bufs[last & 1]; it is copied into out for the later stages.
 // (h_flags != nullptr: block 0 also stores the first nh flags into that pinned host buffer, the frame's

@@ -779,10 +779,6 @@ static void facets_emit(FacetBufs &F, const Subdiv2D::Raw &R, float4 *edges, hip
 // when its ends are more than 1 cm apart, paired with seeds_[i] and coloured from hue = i / cells.
 // Pure host work on the merged seeds: it runs on a worker thread next to the main replay.
 static void cells_colours(CellsWork &W, const std::vector<double> &seeds, int ncell);
-static bool markers_gpu_facets() {   // AOS_MARKERS_GPU_FACETS=1: the markers' facets on the GPU builder
-    static const bool on = getenv("AOS_MARKERS_GPU_FACETS") != nullptr;
-    return on;
-}
 
 static void compute_cells(CellsWork &W, int rect_mode) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -816,59 +812,21 @@ static void compute_cells(CellsWork &W, int rect_mode) {
         y = std::max(ry + margin, std::min(ry + rh - margin, y));
         sd.insert(x, y);   // insertion failures are skipped (voronoi_diagram.cpp:280-285)
     }
-    if (!markers_gpu_facets()) {
-        // getVoronoiFacetList on the worker's own core (calcVoronoi + the facet walk of subdiv2d.cpp, the
-        // host reference of the GPU builder, bit-identical to it): the markers job then needs no stream,
-        // pinned buffers or GPU time of its own; the walk costs the worker a few ms next to its replay
-        std::vector<int> off;
-        std::vector<float> xy;
-        sd.voronoi_facets(off, xy);
-        int ncell = 0;
-        for (size_t f = 0; f + 1 < off.size() && (int)f < ns; ++f) {
-            const int b0 = off[f], n = off[f + 1] - b0;
-            if (n < 3) continue;
-            for (int j = 0; j < n; ++j) { W.cell_xy.push_back(xy[2 * (b0 + j)]); W.cell_xy.push_back(xy[2 * (b0 + j) + 1]); }
-            const double dx = (double)xy[2 * b0] - (double)xy[2 * (b0 + n - 1)];
-            const double dy = (double)xy[2 * b0 + 1] - (double)xy[2 * (b0 + n - 1) + 1];
-            if (std::sqrt(dx * dx + dy * dy) > 0.01) { W.cell_xy.push_back(xy[2 * b0]); W.cell_xy.push_back(xy[2 * b0 + 1]); }
-            W.cell_off.push_back((int32_t)(W.cell_xy.size() / 2));
-            ++ncell;
-        }
-        cells_colours(W, seeds, ncell);
-        W.ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        return;
-    }
-    // getVoronoiFacetList on the GPU (the builder of the main graph, on the worker's stream): the
-    // facet of real vertex k is the start points of its k_facet_emit edges, cnt[k] of them (0 for a
-    // facet of fewer than 2 points: never a cell).
-    AOS_HIP(hipSetDevice(W.device));
-    if (!W.stream) AOS_HIP(hipStreamCreateWithFlags(&W.stream, hipStreamNonBlocking));
-    int *h_sc = static_cast<int *>(W.h.ensure(4096));
-    SyncEvent sev;
-    Subdiv2D::Raw R{};
-    const int ne = facets_count(W.fb, sd, R, h_sc, W.stream, sev);
-    const size_t need = sizeof(float4) * (size_t)std::max(ne, 1) + sizeof(int) * (size_t)R.n_vtx;
-    float4 *d_e = dev<float4>(W.edges, std::max(ne, 1));
-    if (ne) facets_emit(W.fb, R, d_e, W.stream);
-    char *hb = static_cast<char *>(W.h.ensure(need + 4096)) + 4096;   // h_sc stays in the first 4 KiB
-    const float4 *he = reinterpret_cast<const float4 *>(hb);
-    const int *hcnt = reinterpret_cast<const int *>(hb + sizeof(float4) * (size_t)std::max(ne, 1));
-    if (ne) AOS_HIP(hipMemcpyAsync(const_cast<float4 *>(he), d_e, sizeof(float4) * (size_t)ne, hipMemcpyDeviceToHost, W.stream));
-    AOS_HIP(hipMemcpyAsync(const_cast<int *>(hcnt), W.fb.cnt.p, sizeof(int) * (size_t)R.n_vtx, hipMemcpyDeviceToHost, W.stream));
-    AOS_HIP(hipStreamSynchronize(W.stream));
+    // getVoronoiFacetList on the worker's own core (calcVoronoi + the facet walk of subdiv2d.cpp, the host
+    // reference of the main graph's GPU builder, bit-identical to it): the markers job needs no stream, pinned
+    // buffers or GPU time of its own; the walk costs the worker a few ms next to its replay. (The markers'
+    // facets on the GPU builder were kept as AOS_MARKERS_GPU_FACETS=1, removed.)
+    std::vector<int> off;
+    std::vector<float> xy;
+    sd.voronoi_facets(off, xy);
     int ncell = 0;
-    size_t b = 0;
-    for (int k = 4, i = 0; k < R.n_vtx && i < ns; ++k) {
-        if (R.vtype[k] != 0) continue;
-        const int n = hcnt[k];
-        const size_t b0 = b;
-        b += (size_t)n;
-        ++i;
+    for (size_t f = 0; f + 1 < off.size() && (int)f < ns; ++f) {
+        const int b0 = off[f], n = off[f + 1] - b0;
         if (n < 3) continue;
-        for (int j = 0; j < n; ++j) { W.cell_xy.push_back(he[b0 + j].x); W.cell_xy.push_back(he[b0 + j].y); }
-        const float4 f = he[b0], l = he[b0 + n - 1];
-        const double dx = (double)f.x - (double)l.x, dy = (double)f.y - (double)l.y;
-        if (std::sqrt(dx * dx + dy * dy) > 0.01) { W.cell_xy.push_back(f.x); W.cell_xy.push_back(f.y); }
+        for (int j = 0; j < n; ++j) { W.cell_xy.push_back(xy[2 * (b0 + j)]); W.cell_xy.push_back(xy[2 * (b0 + j) + 1]); }
+        const double dx = (double)xy[2 * b0] - (double)xy[2 * (b0 + n - 1)];
+        const double dy = (double)xy[2 * b0 + 1] - (double)xy[2 * (b0 + n - 1) + 1];
+        if (std::sqrt(dx * dx + dy * dy) > 0.01) { W.cell_xy.push_back(xy[2 * b0]); W.cell_xy.push_back(xy[2 * b0 + 1]); }
         W.cell_off.push_back((int32_t)(W.cell_xy.size() / 2));
         ++ncell;
     }
@@ -903,7 +861,6 @@ static void cells_colours(CellsWork &W, const std::vector<double> &seeds, int nc
 static void markers_start(GvdState &G, int rect_mode) {
     if (!G.cells) G.cells.reset(new CellsWork());
     CellsWork &W = *G.cells;
-    AOS_HIP(hipGetDevice(&W.device));
     W.seeds.clear();
     for (size_t i = 0; i + 1 < G.merged_xy.size(); i += 2)
         if (std::isfinite(G.merged_xy[i]) && std::isfinite(G.merged_xy[i + 1])) {

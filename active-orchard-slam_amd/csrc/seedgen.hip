@@ -152,17 +152,12 @@ uint64_t aos_ctx::cloud_for_box(const float b[6]) {
 }
 
 void aos_ctx::upload_pack(void *dst, const aos_cloud_view &v, CloudSplit &sp, bool prefetch) {
-    // chunks of AOS_UP_CHUNK_KB (default 2 MB): the last DMAs start soon after the last gather, so the upload
-    // ends ~one chunk's DMA after the gather instead of one slot per thread later (8 MB slots: ~1 ms)
-    static const uint64_t kChunkPts = [] {
-        const char *e = getenv("AOS_UP_CHUNK_KB");
-        const long kb = e ? std::max(64L, std::min(65536L, atol(e))) : 2048L;
-        return (uint64_t)(kb << 10) / 12;
-    }();
+    // chunks of 2 MB: the last DMAs start soon after the last gather, so the upload ends ~one chunk's DMA after
+    // the gather instead of one slot per thread later (8 MB slots: ~1 ms). Every gather thread copies on a stream
+    // of its own. (Both were measured with AOS_UP_CHUNK_KB and AOS_UP_STREAMS, removed.)
+    constexpr uint64_t kChunkPts = (2048u << 10) / 12;
     const uint64_t n = v.n_points;
     const int nth = up_threads();
-    // AOS_UP_STREAMS (A/B runs): the threads' copies share this many streams (thread t: stream t mod it)
-    static const int n_up_streams = [] { const char *e = getenv("AOS_UP_STREAMS"); return e ? std::max(1, atoi(e)) : kUpThreads; }();
     for (int t = 0; t < nth; ++t)
         if (!up.st[t]) {
             AOS_HIP(hipStreamCreateWithFlags(&up.st[t], hipStreamNonBlocking));
@@ -193,7 +188,7 @@ void aos_ctx::upload_pack(void *dst, const aos_cloud_view &v, CloudSplit &sp, bo
     auto work = [&](int t) {
         try {
             AOS_HIP(hipSetDevice(device));
-            hipStream_t ust = up.st[t % std::min(nth, n_up_streams)];
+            hipStream_t ust = up.st[t];
             if (!prefetch) AOS_HIP(hipStreamWaitEvent(ust, ev[15], 0));
             const uint64_t p0 = std::min(n, per * t), p1 = std::min(n, per * (t + 1));
             float *rr = split ? rest + 3 * p0 + (kPackSlack / 4) * t : nullptr;   // (kPackSlack between runs)
@@ -686,50 +681,36 @@ bool aos_ctx::ror_collect(bool throw_stuck) {
     return u[1] != 0;
 }
 
-// First thinning batch of a whole-map frame: flags reset, opening, after_open (the inflated grid's read-back),
-// batch_n temporal-block launches
-// (launch_next issues them and keeps the caller's launch state). With AOS_THIN_GRAPH != 0 the batch is a
-// hipGraph (BASELINE configs[4]: hipGraph-captured thinning; aos_params.thin_graph), one per batch size,
-// batch_n rounded up to a
-// power of two. A graph bakes every argument in by value, so it is keyed on every pointer and size its
-// nodes hold (the input, opening and ping-pong bit grids, the flags, the tile-activity rows, the host
-// flags buffer when it copies them, and W, H, WW, R, the launch count, the flags length) and re-captured
-// when any of them changes; the per-launch act_prev / act_next alternation is a function of the launch
-// index from 0, the same on every replay. Graph shapes (AOS_THIN_GRAPH, for the diagnosis of round 2's
-// failure, tools/thin_graph_probe.py): 1 (default) the thinning launches only, the opening (which clears the flags)
-// launched just before the graph and the flags read back outside it; 2 round 1's shape: memset node + kernels + D2H copy node; 3 memset node +
-// kernels; 4 clearing kernel + kernels + D2H copy node. Returns true when the graph copied the flags
-// of the batch to h_flags itself.
-bool aos_ctx::thin_first_batch(const FrameGeom &g, const uint64_t *d_ibits, uint64_t *d_open, uint64_t *const bufs[2],
-                               int *d_flags, int *h_flags, int *d_act, int nflags, int &batch_n, int cap_launches,
+// First thinning batch of a whole-map frame: the opening (which clears the flags), after_open (the inflated
+// grid's read-back), then batch_n temporal-block launches (launch_next issues them and keeps the caller's launch
+// state). With aos_params.thin_graph the launches are a hipGraph (BASELINE configs[4]: hipGraph-captured
+// thinning), one per batch size, batch_n rounded up to a power of two. A graph bakes every argument in by
+// value, so it is keyed on every pointer and size its nodes hold (the opened and ping-pong bit grids, the
+// flags, the tile-activity rows, and W, H, WW, R, the launch count, the flags length, the tile count) and
+// re-captured when any of them changes; the per-launch act_prev / act_next alternation is a function of the
+// launch index from 0, the same on every replay. The graph holds the thinning launches only and the flags
+// are read back outside it. (Round 1's shape, a memset node + the opening + the launches + a D2H copy node,
+// wrote garbage into the flags on replay: DESIGN.md "hipGraph-captured first thinning batch". It and the
+// other shapes built to diagnose that, selected with AOS_THIN_GRAPH=2..4, were removed.)
+void aos_ctx::thin_first_batch(const FrameGeom &g, const uint64_t *d_ibits, uint64_t *d_open, uint64_t *const bufs[2],
+                               int *d_flags, int *d_act, int nflags, int &batch_n, int cap_launches,
                                const std::function<void(int)> &launch_next, const std::function<void()> &after_open) {
     hipStream_t s = stream;
-    const int K = kThinItersPerLaunch;
-    if (thin_graph_shape < 0) {
-        const char *e = getenv("AOS_THIN_GRAPH");   // (diagnosis: overrides aos_params.thin_graph)
-        thin_graph_shape = e ? std::max(0, std::min(4, atoi(e))) : (P.thin_graph ? 1 : 0);
-        thin_graph_check = getenv("AOS_THIN_GRAPH_CHECK") != nullptr;
-    }
-    const int shape = thin_graph_shape;
     last_thin_graph = 0;
-    // The opening runs outside the graph (shapes 0 and 1) so that after_open (the inflated grid's read-back) can
-    // be queued behind it: the read-back's blit kernel beside k_open took it from ~40 to 110 us at C3 (round-5
-    // trace); beside thinning the copy meets long, LDS-bound launches instead.
-    if (shape <= 1) {
-        launch_open(d_ibits, d_open, g, s, d_flags, nflags);   // (clears the flags)
-        after_open();
-    }
-    if (shape == 0) {
+    // The opening runs outside the graph so that after_open (the inflated grid's read-back) can be queued behind
+    // it: the read-back's blit kernel beside k_open took it from ~40 to 110 us at C3 (round-5 trace); beside
+    // thinning the copy meets long, LDS-bound launches instead.
+    launch_open(d_ibits, d_open, g, s, d_flags, nflags);   // (clears the flags)
+    after_open();
+    if (!P.thin_graph) {
         launch_next(batch_n);
-        return false;
+        return;
     }
     int bn = 2;
     while (bn < batch_n) bn *= 2;
     batch_n = std::min(bn, cap_launches);
-    const bool memset_node = shape == 2 || shape == 3, copy_node = shape == 2 || shape == 4;
-    const std::array<const void *, 8> ptrs{d_ibits, d_open, bufs[0], bufs[1], d_flags, d_act,
-                                           copy_node ? h_flags : nullptr, nullptr};
-    const std::array<int, 8> dims{g.W, g.H, g.WW, g.R, batch_n, nflags, shape, thin_tiles(g)};
+    const std::array<const void *, 5> ptrs{d_open, bufs[0], bufs[1], d_flags, d_act};
+    const std::array<int, 7> dims{g.W, g.H, g.WW, g.R, batch_n, nflags, thin_tiles(g)};
     ThinGraph *tg = nullptr;
     for (auto &t : thin_graphs)
         if (t.dims[4] == batch_n) tg = &t;
@@ -745,16 +726,7 @@ bool aos_ctx::thin_first_batch(const FrameGeom &g, const uint64_t *d_ibits, uint
         hipGraph_t graph = nullptr;
         AOS_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         try {
-            if (memset_node) {
-                AOS_HIP(hipMemsetAsync(d_flags, 0, sizeof(int) * nflags, s));
-                launch_open(d_ibits, d_open, g, s);
-            } else if (shape == 4) {
-                launch_zero_ints(d_flags, nflags, s);
-                launch_open(d_ibits, d_open, g, s);
-            }   // (shape 1: the opening, which clears the flags, ran before the graph)
             launch_next(batch_n);
-            if (copy_node)
-                AOS_HIP(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * (1 + batch_n * K), hipMemcpyDeviceToHost, s));
         } catch (...) {
             (void)hipStreamEndCapture(s, &graph);
             if (graph) (void)hipGraphDestroy(graph);
@@ -771,9 +743,7 @@ bool aos_ctx::thin_first_batch(const FrameGeom &g, const uint64_t *d_ibits, uint
     } else {
         last_thin_graph = 1;
     }
-    if (shape > 1) after_open();   // (diagnostic shapes: the opening is inside the graph)
     AOS_HIP(hipGraphLaunch(tg->exec, s));
-    return copy_node;
 }
 
 void aos_ctx::thin_graphs_release() {
@@ -781,35 +751,6 @@ void aos_ctx::thin_graphs_release() {
         if (t.exec) (void)hipGraphExecDestroy(t.exec);
     thin_graphs.clear();
 }
-
-// AOS_THIN_GRAPH_CHECK: after the flags read-back, compare the host copy with a fresh synchronous read of
-// the device flags (after a device-wide sync) and check that no flag word holds anything but 0 / 1 and
-// that the words past the iterations run are still 0. Reports to stderr; diagnosis only.
-void aos_ctx::thin_check_flags(const int *d_flags, const int *h_flags, int n_read, int nflags) {
-    AOS_HIP(hipDeviceSynchronize());
-    std::vector<int> dv(nflags);
-    AOS_HIP(hipMemcpy(dv.data(), d_flags, sizeof(int) * nflags, hipMemcpyDeviceToHost));
-    int host_diff = 0, not01 = 0, tail = 0, first = -1;
-    char vals[160] = "";
-    for (int i = 0, nv = 0; i < nflags; ++i) {
-        if (i < n_read && dv[i] != h_flags[i]) { ++host_diff; if (first < 0) first = i; }
-        if (dv[i] != 0 && dv[i] != 1) {
-            ++not01;
-            if (nv < 6) { const size_t l = strlen(vals); snprintf(vals + l, sizeof(vals) - l, " [%d]=0x%08x", i, (unsigned)dv[i]); ++nv; }
-        }
-        if (i >= n_read && dv[i] != 0) ++tail;
-    }
-    ++thin_checks;
-    if (host_diff || not01 || tail) {
-        ++thin_check_failures;
-        fprintf(stderr, "[aos thin check] graph %d shape %d: %d of %d read words differ host vs device (first %d: host %d "
-                        "device %d), %d words not 0/1 (%s), %d nonzero words past the read range\n", last_thin_graph,
-                thin_graph_shape, host_diff, n_read, first, first >= 0 ? h_flags[first] : 0, first >= 0 ? dv[first] : 0,
-                not01, vals, tail);
-    }
-}
-
-static int grid_readback_bits();
 
 void aos_ctx::run_seedgen(bool want_host, aos_seedgen_out &out) {
     // A frame is served (have_frame) only once every check passed: finish_frame sets it before the ROR
@@ -829,7 +770,7 @@ void aos_ctx::run_seedgen(bool want_host, aos_seedgen_out &out) {
 }
 
 bool aos_ctx::run_seedgen_once(bool want_host, aos_seedgen_out &out, bool allow_guess) {
-    const bool trace = getenv("AOS_TRACE") != nullptr;
+    const bool trace = trace_on();
     const auto t_in = std::chrono::steady_clock::now();
     auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count(); };
     std::memset(&out, 0, sizeof(out));
@@ -858,7 +799,7 @@ bool aos_ctx::run_seedgen_once(bool want_host, aos_seedgen_out &out, bool allow_
     // the cluster stage's read-backs (finish_frame sends the skeleton's)
     infl_bits_sent = false;
     auto send_infl_bits = [&]() {
-        if (!want_host || !grid_readback_bits()) return;
+        if (!want_host) return;
         expander.drain();   // (a failed frame's expansion may still read the buffer)
         const size_t nb = 8 * Cw;
         grid_d2h(h_occ_bits.ensure(std::max<size_t>(nb, 8)), d_ibits, nb);
@@ -879,7 +820,8 @@ bool aos_ctx::run_seedgen_once(bool want_host, aos_seedgen_out &out, bool allow_
     // device), so the first batch is sized from the last frame's T (at least 2 launches) and later
     // batches double: a frame pays one host round trip in the common case, a few when T jumps.
     int cap_launches = std::max(3, max_iters / K);
-    if (const char *e = getenv("AOS_DEBUG_THIN_CAP")) cap_launches = std::max(1, atoi(e));   // (tests: force non-convergence)
+    if (const int e = g_debug_thin_cap.load(std::memory_order_relaxed); e >= 0)
+        cap_launches = std::max(1, e);   // (aos_debug_limits: tests force non-convergence)
     int launched = 0;
     const uint64_t *src = d_open;
     ThinOwn whole{0, g.H, 0, g.WW, 1};
@@ -895,83 +837,65 @@ bool aos_ctx::run_seedgen_once(bool want_host, aos_seedgen_out &out, bool allow_
         }
     };
     int batch_n = std::min(cap_launches, std::max(2, (thin_iters_prev + 2 + K - 1) / K));
-    const bool flags_in_graph = thin_first_batch(g, d_ibits, d_open, bufs, d_flags, h_flags, d_act, nflags, batch_n,
-                                                 cap_launches, launch_next, send_infl_bits);
+    thin_first_batch(g, d_ibits, d_open, bufs, d_flags, d_act, nflags, batch_n, cap_launches, launch_next, send_infl_bits);
     launched = batch_n;
     src = bufs[(batch_n - 1) & 1];
-    const uint64_t *final_buf = d_open;
-    int T = 0;
     // No host round trip after the first batch (verdict r02 weak item 9): a device kernel copies the converged
     // launch's buffer (read from the device flags) into thin_out, the flags come back with the frame's later
     // read-backs, and the post-thinning stages run at once. After the frame the host checks convergence (and
     // the ROR overflow); a frame whose T outgrew the first batch runs more launches below and the
-    // post-thinning stages again. AOS_THIN_DEFER=0: wait for the flags here (round 2's order).
-    static const bool defer = [] { const char *e = getenv("AOS_THIN_DEFER"); return !e || atoi(e) != 0; }();
-    bool ror_done = false;
-    int round0 = 0;
-    if (defer && !flags_in_graph) {
-        uint64_t *d_out = static_cast<uint64_t *>(thin_out.ensure(Cw * 8));
-        launch_thin_pick(d_flags, launched, bufs[0], bufs[1], d_out, Cw, s, h_flags, 1 + launched * K);
-        AOS_HIP(hipEventRecord(ev[3], s));
-        skel_bits = d_out;
-        const double t_thin = since();
-        // (the cluster stage asks at its first host wait, when k_thin_pick's h_flags are on the host: a first batch
-        // that thinning outgrew leaves a skeleton that is not final, and its clusters are not worth computing)
-        frame_stale = [h_flags, launched, K] { return thin_iterations(h_flags, launched * K) == 0; };
-        try {
-            finish_frame(g, want_host, nullptr, out);   // (ends with a stream synchronisation: h_flags is on the host)
-        } catch (...) {
-            frame_stale = nullptr;
-            throw;
-        }
+    // post-thinning stages again. (Round 2's order, a wait for the flags here, was kept as AOS_THIN_DEFER=0, removed.)
+    uint64_t *d_out = static_cast<uint64_t *>(thin_out.ensure(Cw * 8));
+    launch_thin_pick(d_flags, launched, bufs[0], bufs[1], d_out, Cw, s, h_flags, 1 + launched * K);
+    AOS_HIP(hipEventRecord(ev[3], s));
+    skel_bits = d_out;
+    double t_thin = since();
+    // (the cluster stage asks at its first host wait, when k_thin_pick's h_flags are on the host: a first batch
+    // that thinning outgrew leaves a skeleton that is not final, and its clusters are not worth computing)
+    frame_stale = [h_flags, launched] { return thin_iterations(h_flags, launched * kThinItersPerLaunch) == 0; };
+    try {
+        finish_frame(g, want_host, nullptr, out);   // (ends with a stream synchronisation: h_flags is on the host)
+    } catch (...) {
         frame_stale = nullptr;
-        if (thin_graph_check) thin_check_flags(d_flags, h_flags, 1 + launched * K, nflags);
-        if (ror_collect()) return true;
-        ror_done = true;
-        // (finish_frame read the binned count before ror_collect set it: the fields that depend on it again)
-        auto ms_ev = [&](int a, int b) { float t = 0; (void)hipEventElapsedTime(&t, ev[a], ev[b]); return t; };
-        out.n_binned = static_cast<const int *>(h_stats.p)[0];
-        out.ms_ror_count = out.n_binned ? ms_ev(10, 11) : 0.0f;
-        out.ms_ror_bin = out.n_binned ? ms_ev(12, 13) : 0.0f;
-        out.ms_ror_scatter = out.n_binned ? ms_ev(14, 10) : 0.0f;
-        T = thin_iterations(h_flags, launched * K);
-        if (T) {
-            last_thin_launches = launched;
-            thin_iters = thin_iters_prev = T;
-            out.thin_iters = T;
-            out.thin_launches = launched;
-            if (trace)
-                fprintf(stderr, "[aos trace seedgen] at %.2f: thin (deferred) %.2f finish %.2f (T %d, launches %d, graph %d)\n",
-                        trace_ms() - since(), t_thin, since(), T, launched, last_thin_graph);
-            return false;
-        }
-        if (launched >= cap_launches) throw std::runtime_error("thinning did not converge");
-        round0 = 1;   // T outgrew the first batch: more launches, then the post-thinning stages again
+        throw;
     }
-    for (int round = round0;; ++round) {
-        if (round > 0) launch_next(batch_n << round);
-        if (round > 0 || !flags_in_graph)
-            AOS_HIP(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * (1 + launched * K), hipMemcpyDeviceToHost, s));
+    frame_stale = nullptr;
+    if (ror_collect()) return true;
+    // (finish_frame read the binned count before ror_collect set it: the fields that depend on it again)
+    auto ms_ev = [&](int a, int b) { float t = 0; (void)hipEventElapsedTime(&t, ev[a], ev[b]); return t; };
+    out.n_binned = static_cast<const int *>(h_stats.p)[0];
+    out.ms_ror_count = out.n_binned ? ms_ev(10, 11) : 0.0f;
+    out.ms_ror_bin = out.n_binned ? ms_ev(12, 13) : 0.0f;
+    out.ms_ror_scatter = out.n_binned ? ms_ev(14, 10) : 0.0f;
+    int T = thin_iterations(h_flags, launched * K);
+    if (T) {
+        last_thin_launches = launched;
+        thin_iters = thin_iters_prev = T;
+        out.thin_iters = T;
+        out.thin_launches = launched;
+        if (trace)
+            fprintf(stderr, "[aos trace seedgen] at %.2f: thin (deferred) %.2f finish %.2f (T %d, launches %d, graph %d)\n",
+                    trace_ms() - since(), t_thin, since(), T, launched, last_thin_graph);
+        return false;
+    }
+    // T outgrew the first batch: more launches (each round doubles), then the post-thinning stages again
+    for (int round = 1; !T; ++round) {
+        if (launched >= cap_launches) throw std::runtime_error("thinning did not converge");
+        launch_next(batch_n << round);
+        AOS_HIP(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * (1 + launched * K), hipMemcpyDeviceToHost, s));
         AOS_HIP(hipStreamSynchronize(s));
-        if (thin_graph_check) thin_check_flags(d_flags, h_flags, 1 + launched * K, nflags);
         T = thin_iterations(h_flags, launched * K);
-        if (T) {
-            // the last launch that ran: launch j runs iff j == 0 or iteration j*K-1 deleted something
-            int last = 0;
-            for (int j = 1; j < launched; ++j)
-                if (h_flags[1 + j * K - 1]) last = j; else break;
-            final_buf = bufs[last & 1];
-            break;
-        }
-        if (launched >= cap_launches) throw std::runtime_error("thinning did not converge");
     }
+    // the last launch that ran: launch j runs iff j == 0 or iteration j*K-1 deleted something
+    int last = 0;
+    for (int j = 1; j < launched; ++j)
+        if (h_flags[1 + j * K - 1]) last = j; else break;
     last_thin_launches = launched;
     thin_iters = T;
     thin_iters_prev = T;
-    skel_bits = final_buf;
+    skel_bits = bufs[last & 1];
     AOS_HIP(hipEventRecord(ev[3], s));
-    const double t_thin = since();
-    if (!ror_done && ror_collect()) return true;   // (the thinning read-back above synchronised the stream)
+    t_thin = since();
     finish_frame(g, want_host, nullptr, out);
     if (trace)
         fprintf(stderr, "[aos trace seedgen] at %.2f: thin-sync %.2f finish %.2f (T %d, launches %d, graph %d)\n",
@@ -979,44 +903,21 @@ bool aos_ctx::run_seedgen_once(bool want_host, aos_seedgen_out &out, bool allow_
     return false;
 }
 
-// The published grids' D2H. Default (AOS_GRID_READBACK=1, round 5): the two bit-packed grids (the inflated
-// grid and the frameless skeleton, W*H/8 bytes each) cross PCIe and host threads expand them to the {0, 100}
-// bytes with the frame / rectangle while the cluster stage runs (grid_host.cpp). Round 4's traces showed the
-// byte grids' D2H as runtime blit kernels (__amd_rocclr_copyBuffer, 0.65 ms per C2 frame, 2.6 ms at C3) that
-// stretched the cluster stage's kernels beside them (k_fg 18 -> 280 us): the bits are 8x fewer bytes through
-// them. AOS_GRID_READBACK=0: the byte grids by hipMemcpyAsync (round 4), or AOS_GRID_COPY_KERNEL=1 by a kernel of
-// grid_copy_blocks() workgroups.
-static int grid_readback_bits() {
-    static const int v = [] { const char *e = getenv("AOS_GRID_READBACK"); return e ? atoi(e) : 1; }();
-    return v;
-}
-static int grid_expand_threads() {   // AOS_GRID_EXPAND_THREADS (default 8)
-    static const int v = [] { const char *e = getenv("AOS_GRID_EXPAND_THREADS"); return e ? std::max(1, atoi(e)) : 8; }();
-    return v;
-}
+// The published grids' D2H (round 5): the two bit-packed grids (the inflated grid and the frameless skeleton,
+// W*H/8 bytes each) cross PCIe and host threads expand them to the {0, 100} bytes with the frame / rectangle
+// while the cluster stage runs (grid_host.cpp). Round 4's traces showed the byte grids' D2H as runtime blit
+// kernels (__amd_rocclr_copyBuffer, 0.65 ms per C2 frame, 2.6 ms at C3) that stretched the cluster stage's
+// kernels beside them (k_fg 18 -> 280 us): the bits are 8x fewer bytes through them. (Round 4's byte grids by
+// hipMemcpyAsync or by a copy kernel were kept as AOS_GRID_READBACK=0 / AOS_GRID_COPY_KERNEL=1, removed.)
+constexpr int kGridExpandThreads = 8;   // (was measured with AOS_GRID_EXPAND_THREADS, removed)
 // The grids' D2H runs as the runtime's blit kernels (under the HIP runtime torch loads). Beside the cluster stage
 // they held the CUs its kernels needed: k_fg took 45 us instead of 18.6 beside the 2 MB bits copy at C2, 159
-// instead of 24 beside the 8 MB at C3 (round-5 traces, tools/kt_overlap.py). AOS_COPY_CUS = k > 0 creates the copy
-// stream with a CU mask (hipExtStreamCreateWithCUMask) of k CUs spread over the id range, so its blit waves stay
-// there. Measured and not adopted (profiles/r05g_copy_cus_ab.txt): with 16 CUs seed-gen took 1.47-1.49 ms per C2
-// frame instead of 1.24-1.27 (thinning and k_fg slower beside the masked copy). Default 0: no mask; the copies are
-// placed where they meet the fewest kernels instead (the inflated grid beside thinning, the skeleton after k_fg).
-static void create_copy_stream(hipStream_t *st) {
-    static const int want = [] { const char *e = getenv("AOS_COPY_CUS"); return e ? std::max(0, atoi(e)) : 0; }();
-    int dev = 0, ncu = 0;
-    AOS_HIP(hipGetDevice(&dev));
-    AOS_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    if (want <= 0 || want >= ncu) {
-        AOS_HIP(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
-        return;
-    }
-    std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
-    for (int k = 0; k < want; ++k) {
-        const int cu = (int)((long long)k * ncu / want);
-        mask[cu >> 5] |= 1u << (cu & 31);
-    }
-    AOS_HIP(hipExtStreamCreateWithCUMask(st, (uint32_t)mask.size(), mask.data()));
-}
+// instead of 24 beside the 8 MB at C3 (round-5 traces, tools/kt_overlap.py). A copy stream with a CU mask
+// (hipExtStreamCreateWithCUMask, k CUs spread over the id range so that its blit waves stay there) was measured
+// with AOS_COPY_CUS, removed, and not adopted (profiles/r05g_copy_cus_ab.txt): with 16 CUs seed-gen took
+// 1.47-1.49 ms per C2 frame instead of 1.24-1.27 (thinning and k_fg slower beside the masked copy). The stream
+// has no mask; the copies are placed where they meet the fewest kernels instead (the inflated grid beside
+// thinning, the skeleton after k_fg).
 void aos_ctx::grid_d2h(void *h, const void *d, size_t bytes) {
     grid_copy_wait();
     AOS_HIP(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, copy_stream));
@@ -1024,20 +925,12 @@ void aos_ctx::grid_d2h(void *h, const void *d, size_t bytes) {
 // the copy stream (created on first use) waits for the work queued on the handle's stream so far
 void aos_ctx::grid_copy_wait() {
     if (!copy_stream) {
-        create_copy_stream(&copy_stream);
+        AOS_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
         AOS_HIP(hipEventCreateWithFlags(&copy_ready, hipEventDisableTiming));
         AOS_HIP(hipEventCreateWithFlags(&copy_done, hipEventDisableTiming));
     }
     AOS_HIP(hipEventRecord(copy_ready, stream));
     AOS_HIP(hipStreamWaitEvent(copy_stream, copy_ready, 0));
-}
-static int grid_copy_blocks() {   // AOS_GRID_COPY_BLOCKS (default 64)
-    static const int b = [] { const char *e = getenv("AOS_GRID_COPY_BLOCKS"); return e ? std::max(1, atoi(e)) : 64; }();
-    return b;
-}
-static bool grid_copy_kernel() {
-    static const bool on = [] { const char *e = getenv("AOS_GRID_COPY_KERNEL"); return e && atoi(e) != 0; }();
-    return on;
 }
 
 // a16 + a8-a15 on the whole map from skel_bits / occ_bytes, then the frame outputs. clipped_total:
@@ -1069,87 +962,72 @@ void aos_ctx::finish_frame(const FrameGeom &g, bool want_host, const uint64_t *c
         w2g(static_cast<float>(hminx - margin), static_cast<float>(hminy - margin), rect[0], rect[1]);
         w2g(static_cast<float>(hmaxx + margin), static_cast<float>(hmaxy + margin), rect[2], rect[3]);
     }
-    // the two published grids go to host memory on the copy stream while the cluster / seed stage runs
-    // (AOS_GRID_COPY=1: after it instead; the copy's blit kernels share the CUs with the stage's kernels)
-    static const int grid_copy_mode = [] { const char *e = getenv("AOS_GRID_COPY"); return e ? atoi(e) : 0; }();
-    const bool as_bits = grid_readback_bits() != 0;
+    // the two published grids go to host memory, as bits, on the copy stream while the cluster / seed stage runs
+    // (the copy's blit kernels share the CUs with the stage's kernels; issuing it after the stage instead was kept
+    // as AOS_GRID_COPY=1, removed)
     auto issue_grid_copy = [&]() {
         // (a failed frame's expansion may still write h_occ / h_skel and read the bit buffers: drained before
         // any of them can be reallocated; ADVICE r05. A no-op when the inflated bits' send drained it.)
         expander.drain();
         h_occ.ensure(std::max<size_t>(C, 1)); h_skel.ensure(std::max<size_t>(C, 1));
-        if (as_bits) {
-            const size_t nb = 8 * (size_t)g.WW * g.H;
-            uint64_t *hob = static_cast<uint64_t *>(h_occ_bits.ensure(std::max<size_t>(nb, 8)));
-            uint64_t *hsb = static_cast<uint64_t *>(h_skel_bits.ensure(std::max<size_t>(nb, 8)));
-            if (!infl_bits_sent)   // (a tiled frame: the gathered inflated grid)
-                grid_d2h(hob, tiled_frame ? full_infl.as<uint64_t>() : infl_bits.as<uint64_t>(), nb);
-            grid_d2h(hsb, skel_bits, nb);
-            AOS_HIP(hipEventRecord(copy_done, copy_stream));
-            GridExpander::Job j{};
-            const int dev = device;
-            hipEvent_t e = copy_done;
-            j.wait = [dev, e] {
-                AOS_HIP(hipSetDevice(dev));
-                AOS_HIP(hipEventSynchronize(e));
-            };
-            j.occ_bits = hob; j.skel_bits = hsb;
-            j.occ = h_occ.as<int8_t>(); j.skel = h_skel.as<int8_t>();
-            j.W = g.W; j.H = g.H; j.WW = g.WW; j.frame = 5;
-            j.rect[0] = rect[0]; j.rect[1] = rect[1]; j.rect[2] = rect[2]; j.rect[3] = rect[3];
-            j.threads = grid_expand_threads();
-            expander.start(j);
-        } else if (grid_copy_kernel()) {   // (a kernel launch never holds the host; see copy_kernel_bulk)
-            grid_copy_wait();
-            copy_kernel_bulk(h_occ.p, d_occ, C, grid_copy_blocks(), copy_stream);
-            copy_kernel_bulk(h_skel.p, d_skel, C, grid_copy_blocks(), copy_stream);
-        } else {
-            grid_d2h(h_occ.p, d_occ, C);
-            grid_d2h(h_skel.p, d_skel, C);
-        }
+        const size_t nb = 8 * (size_t)g.WW * g.H;
+        uint64_t *hob = static_cast<uint64_t *>(h_occ_bits.ensure(std::max<size_t>(nb, 8)));
+        uint64_t *hsb = static_cast<uint64_t *>(h_skel_bits.ensure(std::max<size_t>(nb, 8)));
+        if (!infl_bits_sent)   // (a tiled frame: the gathered inflated grid)
+            grid_d2h(hob, tiled_frame ? full_infl.as<uint64_t>() : infl_bits.as<uint64_t>(), nb);
+        grid_d2h(hsb, skel_bits, nb);
+        AOS_HIP(hipEventRecord(copy_done, copy_stream));
+        GridExpander::Job j{};
+        const int dev = device;
+        hipEvent_t e = copy_done;
+        j.wait = [dev, e] {
+            AOS_HIP(hipSetDevice(dev));
+            AOS_HIP(hipEventSynchronize(e));
+        };
+        j.occ_bits = hob; j.skel_bits = hsb;
+        j.occ = h_occ.as<int8_t>(); j.skel = h_skel.as<int8_t>();
+        j.W = g.W; j.H = g.H; j.WW = g.WW; j.frame = 5;
+        j.rect[0] = rect[0]; j.rect[1] = rect[1]; j.rect[2] = rect[2]; j.rect[3] = rect[3];
+        j.threads = kGridExpandThreads;
+        expander.start(j);
     };
     HostTrace tr{"finish"};
     launch_bits_to_bytes(skel_bits, d_skel, g, 0, s, rect);   // (a16: the rectangle drawn in the same launch)
     // the bits go once the cluster stage has queued k_fg and its count read-back (SeedStageIn::after_fg; round 5
     // traces: beside k_fg the copy's blit kernel took k_fg from 19 to 49 us, and the read-back waited behind it on
-    // PCIe); the byte copies of the other modes right away
+    // PCIe)
     bool copy_issued = false;
     auto copy_now = [&]() {
         if (copy_issued) return;
         copy_issued = true;
         issue_grid_copy();
     };
-    if (want_host && grid_copy_mode == 0 && !as_bits) copy_now();
     tr.mark("copy_issued");
 
     // ---------------- a8-a15 clusters, tree rows, seeds
     SeedStageIn sin{skel_bits, &geom, &poly, P.cluster_min_length, pre};
-    if (want_host && grid_copy_mode == 0 && as_bits) {
+    if (want_host) {
         sin.after_fg = copy_now;
-        // the replays walk the skeleton's bits once their read-back (queued by after_fg) is done
-        static const bool replay_bits = [] { const char *e = getenv("AOS_REPLAY_BITS"); return !e || atoi(e) != 0; }();
-        if (replay_bits)
-            sin.host_skel_bits = [&]() -> const uint64_t * {
-                if (!copy_issued) return nullptr;
-                AOS_HIP(hipEventSynchronize(copy_done));
-                return static_cast<const uint64_t *>(h_skel_bits.p);
-            };
+        // the replays walk the skeleton's bits once their read-back (queued by after_fg) is done (replays from the
+        // clusters' cells instead were kept as AOS_REPLAY_BITS=0, removed)
+        sin.host_skel_bits = [&]() -> const uint64_t * {
+            if (!copy_issued) return nullptr;
+            AOS_HIP(hipEventSynchronize(copy_done));
+            return static_cast<const uint64_t *>(h_skel_bits.p);
+        };
     }
     sin.stale = frame_stale;
     SeedStageOut so;
     run_cluster_seed_stage(cs, sin, so, s, ev[4], trace_on() ? &ev[16] : nullptr);
     AOS_HIP(hipEventRecord(ev[5], s));
-    if (want_host && (grid_copy_mode == 1 || as_bits)) copy_now();   // (a stage that did not call after_fg)
+    if (want_host) copy_now();   // (a stage that did not call after_fg)
 
     unsigned long long *h_cnt = static_cast<unsigned long long *>(h_stats.ensure(64 + 8 * kRorCounters)) + 8;
     if (!clipped_total) AOS_HIP(hipMemcpyAsync(h_cnt, counters.p, 8 * kRorCounters, hipMemcpyDeviceToHost, s));
     tr.mark("stage_done");
     AOS_HIP(hipStreamSynchronize(s));
     tr.mark("stream_synced");
-    if (want_host) {
-        if (as_bits) expander.join();   // (rethrows a failed wait)
-        else AOS_HIP(hipStreamSynchronize(copy_stream));
-    }
+    if (want_host) expander.join();   // (rethrows a failed wait)
     tr.mark("copies_synced");
     if (clipped_total) {
         n_clipped = *clipped_total;

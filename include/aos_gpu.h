@@ -453,6 +453,12 @@ void aos_debug_faults(int32_t ror_stuck_rank, uint64_t a2a_round_bytes);
  * (default 0: 64), so tests reach the fallback. replay_all != 0: every cluster is replayed, also those with the
  * order-free certificate (whose records the replay must reproduce). (-1, 0, 0): the defaults. */
 void aos_debug_replay(int32_t gpu_min_clusters, int32_t ring_cap, int32_t replay_all);
+/* Test hook (process-wide; a negative value restores the default): thin_cap_launches >= 0: a whole-map frame
+ * issues at most max(1, thin_cap_launches) thinning launches, so a test reaches "thinning did not converge";
+ * ccl_edge_cap >= 0: the cluster stage's link list holds max(2, ccl_edge_cap) links, so a test reaches its
+ * overflow fall-back; stats_lds == 0: the cluster statistics kernel reads the cluster table from global memory
+ * instead of its LDS copy. (-1, -1, -1): the defaults. */
+void aos_debug_limits(int32_t thin_cap_launches, int32_t ccl_edge_cap, int32_t stats_lds);
 /* Diagnostics: the last single-GPU seed-gen frame's exact BFS replays: out[0] = all of them (n_bfs_replayed),
  * out[1] = on the GPU, out[2] = on host threads over the skeleton bits, out[3] = on host threads from the clusters'
  * cells. */

@@ -21,7 +21,7 @@ POLY_X0 = POLY_Y0 = 256.0
 ORIGIN = POLY_X0 - MARGIN * RES   # 253.5
 
 # the library's constants the predictors use
-CCL_CHUNK = 2048       # csrc/cluster_seed.hip:109  ccl_chunk()
+CCL_CHUNK = 2048       # csrc/cluster_seed.hip:111  kCclChunk
 CCL_EDGE_LDS = 1024    # csrc/cluster_seed.hip:120  kCclEdgeLds
 CCL_ECAP_MIN = 4096    # csrc/cluster_seed.hip:117  ccl_edge_cap: max(4096, nf / 4)
 CL_COUNT_TB = 256      # csrc/cluster_seed.hip:294  kClTB (cells per k_cluster_count block)

@@ -484,36 +484,40 @@ def test_gvd_markers_background_job_overlaps_next_frame():
     c.close()                     # job still in flight
 
 
-def test_ccl_link_list_overflow_fallback(monkeypatch):
+def test_ccl_link_list_overflow_fallback():
     """k_ccl_local hands its cross-chunk links to k_ccl_cross through a list; when the list overflows, the same
-    launch unions every link of every cell instead. A C1 frame with a 2-entry list (AOS_DEBUG_CCL_ECAP) equals
+    launch unions every link of every cell instead. A C1 frame with a 2-entry list (aos_debug_limits) equals
     the default frame, clusters and seeds included."""
     cfg = orchard.CONFIGS["C1"]
     cloud, poly = orchard.generate(cfg), orchard.polygon(cfg)
     ctx = aos_gpu.Ctx(aos_gpu.default_params(grid_resolution=cfg.res))
     ctx.set_polygon(poly)
     a = ctx.seedgen(cloud)
-    monkeypatch.setenv("AOS_DEBUG_CCL_ECAP", "2")
-    b = ctx.seedgen(cloud)
-    monkeypatch.delenv("AOS_DEBUG_CCL_ECAP")
+    aos_gpu.debug_limits(ccl_edge_cap=2)
+    try:
+        b = ctx.seedgen(cloud)
+    finally:
+        aos_gpu.debug_limits()
     ctx.close()
     assert a["n_clusters_all"] == b["n_clusters_all"] and a["n_bfs_replayed"] == b["n_bfs_replayed"]
     for k in ("row_center", "row_start", "row_end", "row_length", "voronoi_seeds", "cluster_info", "rows_info"):
         assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), k
 
 
-def test_cluster_stats_global_memory_path(monkeypatch):
+def test_cluster_stats_global_memory_path():
     """k_cluster_stats keeps a cluster's cells in LDS when it fits (kStatLds cells, grids below 65536 columns and
-    rows) and otherwise reads global memory in every pass. A C1 frame with the LDS copy off (AOS_DEBUG_STATS_LDS=0)
-    equals the default frame: records, replays, rows and seeds."""
+    rows) and otherwise reads global memory in every pass. A C1 frame with the LDS copy off (aos_debug_limits,
+    stats_lds = 0) equals the default frame: records, replays, rows and seeds."""
     cfg = orchard.CONFIGS["C1"]
     cloud, poly = orchard.generate(cfg), orchard.polygon(cfg)
     ctx = aos_gpu.Ctx(aos_gpu.default_params(grid_resolution=cfg.res))
     ctx.set_polygon(poly)
     a = ctx.seedgen(cloud)
-    monkeypatch.setenv("AOS_DEBUG_STATS_LDS", "0")
-    b = ctx.seedgen(cloud)
-    monkeypatch.delenv("AOS_DEBUG_STATS_LDS")
+    aos_gpu.debug_limits(stats_lds=0)
+    try:
+        b = ctx.seedgen(cloud)
+    finally:
+        aos_gpu.debug_limits()
     ctx.close()
     assert a["n_clusters_all"] == b["n_clusters_all"] and a["n_bfs_replayed"] == b["n_bfs_replayed"]
     for k in ("row_center", "row_start", "row_end", "row_length", "voronoi_seeds", "cluster_info", "rows_info"):

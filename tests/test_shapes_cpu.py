@@ -30,7 +30,7 @@ def timed_oracle(pattern, R, polygon=None, scene=None):
 
 
 @pytest.mark.parametrize("text,path,value", [
-    (r"e \? std::max\(64, std::min\(16384, atoi\(e\)\)\) : (\d+);", "cluster_seed.hip", S.CCL_CHUNK),
+    (r"static const int kCclChunk = (\d+);", "cluster_seed.hip", S.CCL_CHUNK),
     (r"constexpr int kCclEdgeLds = (\d+);", "cluster_seed.hip", S.CCL_EDGE_LDS),
     (r"std::max\((\d+), nf / 4\)", "cluster_seed.hip", S.CCL_ECAP_MIN),
     (r"constexpr int kClTB = (\d+),", "cluster_seed.hip", S.CL_COUNT_TB),

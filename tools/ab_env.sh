@@ -2,7 +2,7 @@
 # Kernel-trace A/B of environment settings on the C2 bench: for each entry of AB_SETS (space separated; an entry
 # is VAR=value[,VAR=value...], "-" for none) one rocprofv3 --kernel-trace run, then the per-frame trace line and
 # the kernels matching KERNELS (a grep -E pattern) from tools/kt_summary.py. Lines go to gpurun_out/${TAG}_abenv.txt.
-# Usage: TAG=r05j AB_SETS="- AOS_CCL_TB=1024 AOS_CCL_CHUNK=1024" KERNELS="k_ccl" bash tools/ab_env.sh
+# Usage: TAG=r05j AB_SETS="- AOS_STAGED_TOUCH=0 AOS_UP_SPLIT=0" KERNELS="k_rt" bash tools/ab_env.sh
 set -e
 TAG=${TAG:-r05x}
 R=$PWD
