@@ -64,6 +64,25 @@ def assert_gvd_full_parity(ctx, g: dict, o: dict):
         assert np.array_equal(m[k], o[k], equal_nan=True), f"markers' {k} differ"
 
 
+def binned_box(poly, ror_radius=0.2, minz=-0.4, maxz=0.5):
+    """seedgen.hip binned_box / ror_stage: frame_geom's float bounds (polygon +- 2.5 m, double -> float)
+    minus / plus ror_margin, in float32 as on the host."""
+    f = np.float32
+    m = f(f(ror_radius * 1.01) + f(1e-4))
+    minx, maxx = f(poly[:, 0].min() - 2.5), f(poly[:, 0].max() + 2.5)
+    miny, maxy = f(poly[:, 1].min() - 2.5), f(poly[:, 1].max() + 2.5)
+    return [f(minx - m), f(maxx + m), f(miny - m), f(maxy + m), f(f(minz) - m), f(f(maxz) + m)]
+
+
+def inside(cloud, box):
+    import orchard
+    p = orchard.xyz(cloud).astype(np.float32)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    with np.errstate(invalid="ignore"):
+        return int(np.count_nonzero((x >= box[0]) & (x <= box[1]) & (y >= box[2]) & (y <= box[3]) &
+                                    (z >= box[4]) & (z <= box[5])))
+
+
 def sha_of(a, dt):
     """SHA-256 of an array as tools/make_golden.py hashes it (dtype, shape, bytes)."""
     import hashlib

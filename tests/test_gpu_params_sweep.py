@@ -9,7 +9,7 @@ import pytest
 import aos_gpu
 import oracle_py as O
 import orchard
-from parity_util import assert_gvd_parity, assert_seedgen_parity
+from parity_util import assert_gvd_parity, assert_seedgen_parity, grid_diff
 
 pytestmark = pytest.mark.gpu
 
@@ -44,6 +44,9 @@ def test_random_parameters_full_frame(seed):
     okw = {_ORACLE_NAME.get(k, k): v for k, v in kw.items()}
     o = O.seedgen(cloud, poly, O.default_params(**okw), is_dense=dense)
     assert_seedgen_parity(g, o)
+    # the raster before inflation (single cells show) and the clipped count
+    assert grid_diff(c.debug_grid("raster", (o["height"], o["width"])) != 0, o["raster"] != 0) == 0
+    assert g["n_clipped"] == o["n_clipped"], (g["n_clipped"], o["n_clipped"])
     gg = c.gvd_from_seedgen()
     og = O.gvd(o["voronoi_seeds"], o["rows_info"], o, O.default_params(markers=1, **okw))
     assert_gvd_parity(gg, og)
