@@ -27,6 +27,23 @@ def assert_seedgen_parity(g: dict, o: dict, check_grids=True):
     return all(np.array_equal(g[k], o[k]) for k in ("voronoi_seeds", "rows_info", "cluster_info"))
 
 
+def assert_seeds_exact(g: dict, o: dict):
+    """DESIGN §2's claim for the row, ray and seed stage: the rows, the three seed lists and their concatenation, the
+    sorted outputs and the three counts equal the oracle's bit for bit."""
+    for k in ("row_center", "row_start", "row_end", "row_length", "virtual_seeds", "ray_seeds", "endpoint_seeds",
+              "voronoi_seeds", "rows_info", "cluster_info"):
+        assert g[k].shape == o[k].shape, (k, g[k].shape, o[k].shape)
+        assert g[k].dtype == o[k].dtype == np.float64, (k, g[k].dtype, o[k].dtype)
+        if not np.array_equal(g[k], o[k]):
+            bad = np.nonzero((g[k] != o[k]).reshape(len(g[k]), -1).any(axis=1))[0]
+            hexes = lambda a: [float(v).hex() for v in np.atleast_1d(a)]   # noqa: E731
+            raise AssertionError(f"{k}: {len(bad)} of {len(g[k])} entries differ, first at {bad[0]}: "
+                                 f"{hexes(g[k][bad[0]])} vs the oracle's {hexes(o[k][bad[0]])}")
+    assert (g["n_virtual"], g["n_ray"], g["n_endpoint"]) == \
+        (len(o["virtual_seeds"]), len(o["ray_seeds"]), len(o["endpoint_seeds"]))
+    assert len(g["voronoi_seeds"]) == len(o["virtual_seeds"]) + len(o["ray_seeds"]) + len(o["endpoint_seeds"])
+
+
 def assert_gvd_parity(g: dict, o: dict):
     assert g["published"] == o["published"]
     if not o["published"]:

@@ -40,19 +40,30 @@ _AOS_ONLY = ("thin_graph", "gvd_markers", "gvd_count_evals", "max_graph_publish_
 
 
 # ---------------------------------------------------------------- scene
-def rect_polygon(W, H):
-    x1, y1 = POLY_X0 + (W - 2 * MARGIN) * RES, POLY_Y0 + (H - 2 * MARGIN) * RES
+def margin_cells(res=RES):
+    """getActiveBounds' 2.5 m margin in cells of `res`, which must divide it (MARGIN at RES)."""
+    m = 2.5 / res
+    if m != int(m) or np.float32(res) != res:
+        raise ValueError(f"res = {res}: a float32 binary fraction that divides the 2.5 m margin is needed")
+    return int(m)
+
+
+def rect_polygon(W, H, res=RES):
+    m = margin_cells(res)
+    x1, y1 = POLY_X0 + (W - 2 * m) * res, POLY_Y0 + (H - 2 * m) * res
     return np.array([[POLY_X0, POLY_Y0], [x1, POLY_Y0], [x1, y1], [POLY_X0, y1]], np.float64)
 
 
-def scene(pattern, R, polygon=None, **params):
+def scene(pattern, R, polygon=None, res=RES, **params):
     """(cloud, polygon, aos_kwargs, oracle_kwargs) of the frame whose raster is `pattern` (the whole H x W grid;
-    the polygon spans cells [10, W - 10) x [10, H - 10)). polygon= overrides the rectangle with the same box."""
+    the polygon spans cells [10, W - 10) x [10, H - 10)). polygon= overrides the rectangle with the same box.
+    res= another grid resolution (0.15625, 0.3125, 0.5: the margin is then 2.5 / res cells instead of 10)."""
     pattern = np.asarray(pattern)
     H, W = pattern.shape
-    if W <= 2 * MARGIN or H <= 2 * MARGIN:
-        raise ValueError(f"pattern {W} x {H}: the grid is the polygon's box plus {MARGIN} cells on every side")
-    rect = rect_polygon(W, H)
+    margin = margin_cells(res)
+    if W <= 2 * margin or H <= 2 * margin:
+        raise ValueError(f"pattern {W} x {H}: the grid is the polygon's box plus {margin} cells on every side")
+    rect = rect_polygon(W, H, res)
     if polygon is None:
         polygon = rect
     else:
@@ -62,11 +73,11 @@ def scene(pattern, R, polygon=None, **params):
     ys, xs = np.nonzero(pattern)
     pts = np.zeros((3 * len(xs), 4), np.float32)
     for k, z in enumerate((0.0, 0.01, 0.02)):
-        pts[k::3, 0] = ORIGIN + (xs + 0.5) * RES
-        pts[k::3, 1] = ORIGIN + (ys + 0.5) * RES
+        pts[k::3, 0] = ORIGIN + (xs + 0.5) * res
+        pts[k::3, 1] = ORIGIN + (ys + 0.5) * res
         pts[k::3, 2] = z
     cloud = pts.view(np.uint8).reshape(-1, 16)
-    akw = dict(grid_resolution=RES, inflation_radius=RES * R + 0.01, **params)
+    akw = dict(grid_resolution=res, inflation_radius=res * R + 0.01, **params)
     okw = {_ORACLE_NAME.get(k, k): v for k, v in akw.items() if k not in _AOS_ONLY}
     return cloud, polygon, akw, okw
 
