@@ -1,4 +1,5 @@
-// Per-handle state of libaos_gpu.so. Not part of the ABI.
+// Per-handle state of libaos_gpu.so. Not part of the ABI. Every buffer member frees itself with the handle;
+// release() (seedgen.hip) stops the threads and destroys the streams and events first.
 #pragma once
 #include <array>
 #include <condition_variable>
@@ -13,6 +14,7 @@
 #include "aos_internal.h"
 #include "cluster_seed.h"
 #include "grid_host.h"
+#include "gvd.h"
 #include "host_pool.h"
 
 struct aos_ctx {
@@ -63,7 +65,7 @@ struct aos_ctx {
     uint64_t map_scan_begin = 0;     // map points before the last aos_map_append
 
     // ---- device buffers
-    aos::DevBuf cloud_copy, bin_count, bin_start, sorted, ror_scratch, ror_bigbins, scan_tmp, counters;
+    aos::DevBuf cloud_copy, bin_count, bin_start, sorted, ror_scratch, ror_bigbins, counters;
     aos::DevBuf raster_bits, infl_bits, open_bits, thin_a, thin_b, thin_act, occ_bytes, skel_bytes, flags;
     aos::DevBuf thin_out;   // the converged skeleton bits, picked on the device (launch_thin_pick)
     aos::LookBackScratch ror_lb;           // look-back words of the ROR column scan (k_rt_colscan)
@@ -167,7 +169,7 @@ struct aos_ctx {
     std::vector<double> h_row_center, h_row_start, h_row_end, h_row_length, h_voronoi, h_rows_info, h_cluster_info;
     int n_virtual = 0, n_ray = 0, n_endpoint = 0, n_clusters_all = 0, n_bfs_replayed = 0;
 
-    // ---- GVD (gvd.hip)
+    // ---- GVD (gvd.hip: the stage; gvd_handle.hip: these methods)
     bool have_gvd = false, gvd_from_frame = false;
     uint64_t frame_gen = 0, gvd_frame_gen = 0, gvd_gen = 0;   // seed-gen frames / GVD calls so far
     const int8_t *gvd_skel = nullptr;                          // the skeleton the last GVD call used
@@ -251,6 +253,6 @@ struct aos_ctx {
 };
 
 namespace aos {
-// aos_gvd_wait: collects the pipelined GVD job's graph into out; 0 if no job was started (gvd.hip)
+// aos_gvd_wait: collects the pipelined GVD job's graph into out; 0 if no job was started (gvd_handle.hip)
 int gvd_wait_out(aos_ctx *c, aos_gvd_out *out);
 }  // namespace aos

@@ -1,18 +1,14 @@
-// Cluster / tree-row / seed stage and GVD stage state. Not part of the ABI.
+// Cluster / tree-row / seed stage state and the greedy de-duplication both stages share (the GVD stage's state:
+// gvd.h). Not part of the ABI.
 #pragma once
+#include <atomic>
 #include <climits>
-#include <condition_variable>
-#include <exception>
 #include <functional>
-#include <memory>
-#include <mutex>
-#include <thread>
 #include <vector>
 
 #include "aos_internal.h"
 #include "dev_prims.h"
 #include "host_pool.h"
-#include "subdiv2d.h"
 
 namespace aos {
 
@@ -58,7 +54,7 @@ struct DedupScratch {
     CellScratch cells;
     CellIdx ci{};          // the cell index of the last de-duplication (the GVD merge finds members through it)
     LookBackScratch lb;
-    DevBuf state, misc;
+    DevBuf state;
     unsigned epoch = 0;    // of the state words
     SyncEvent sev;
 };
@@ -70,9 +66,6 @@ struct DedupScratch {
 // in out or -1 (the GVD graph finds boundary points through the de-duplication's own index, S.ci).
 void greedy_dedup_async(DedupScratch &S, const double2 *cand, const int *ok, int n, int mode, double thr, const HashG &h,
                         double2 *out, int *kept_index, int *owner, int *d_count, hipStream_t s, int *pos_of = nullptr);
-// The same, then waits and returns the kept count (h_scalar: 2 pinned ints).
-int greedy_dedup(DedupScratch &S, const double2 *cand, const int *ok, int n, int mode, double thr, const HashG &h,
-                 double2 *out, int *kept_index_out, hipStream_t s, int *h_scalar);
 // Problems of at most kSmallMax candidates (up to 2 per launch), one workgroup each, the index and the
 // rounds in LDS: one launch. h: small_hash (at most 2048 buckets).
 constexpr int kSmallMax = 4096;
@@ -89,7 +82,8 @@ struct ClusterSeedState {
     DevBuf fg_bits, word_cnt, word_off, fg_list, parent, root_flag, root_rank, cl_count, cl_off, cl_cursor, cl_cells;
     DevBuf ccl_edges;   // k_ccl_local's cross-chunk links: count, pad, then (i, j) pairs
     DevBuf rec, row_idx, poly, cur_tab;
-    DevBuf cand_xy, cand_ok, cand_state, hash_count, hash_start, hash_slot, hash_sorted, seed_out, misc, scan_tmp;
+    DevBuf cand_xy, cand_ok, seed_out, misc;
+    DevBuf cand_kept;   // the de-duplicated virtual seeds, then the ray and the endpoint seeds (k_concat3's three inputs)
     LookBackScratch lb;           // the stage's single-pass scans
     bool cl_count_dirty = true;   // cl_count (cluster sizes) not known to be zero
     PinnedBuf h_recbuf, h_up_poly, h_up_rows;   // cluster records read back; host -> device staging
@@ -218,85 +212,5 @@ int cluster_union(int W, int H, int n_pieces, const int *piece_root, int n_borde
                   int *piece_cluster);
 void cluster_dist(ClusterDistState &D, FrameComm &fc, const TilePlan &t, const FrameGeom &g, const Poly &poly,
                   float min_len, const uint64_t *win, int root, hipStream_t s, PreClusters &pre, ClusterDistStats &st);
-
-// ------------------------------------------------------------------ GVD
-// publishMarkers' Voronoi cells, computed by a worker thread next to the main Subdiv2D replay. It
-// lives in its own cache-line-aligned heap object: the two replays write their state on every step,
-// and sharing lines with the main replay's fields slowed both down by ~40 % on the EPYC host.
-// Device buffers of the facet builder (calcVoronoi + getVoronoiFacetList on the GPU, gvd.hip).
-// raw = the exported Subdiv2D state in one buffer (quad-edges | points | firstEdge | type), one H2D copy
-struct FacetBufs { DevBuf raw, face, cnt, off, scan_tmp; LookBackScratch lb; PinnedBuf h_stage; int *qe = nullptr, *vf = nullptr, *vt = nullptr; };
-
-struct alignas(128) CellsWork {
-    Subdiv2D sd;                               // extractCellBoundaries' Subdiv2D
-    std::vector<double> seeds;                 // VoronoiDiagram::seeds_ (finite merged seeds)
-    std::vector<double> cell_xy, cell_center;
-    std::vector<int32_t> cell_off;
-    std::vector<float> cell_rgba;
-    float ms = 0;
-    // One persistent worker per handle: it sleeps between frames and keeps its core (and the
-    // replay's ~6 MB of quad-edges in that core's caches); a thread per frame landed on a cold core.
-    std::thread worker;
-    std::mutex mu;
-    std::condition_variable cv;
-    bool busy = false, quit = false;
-    int rect_mode = 0;
-    std::exception_ptr err;     // the last job's error (markers_wait raises or discards it)
-    CellsWork() = default;
-    CellsWork(const CellsWork &) = delete;
-    CellsWork &operator=(const CellsWork &) = delete;
-    ~CellsWork() {
-        if (worker.joinable()) {
-            { std::lock_guard<std::mutex> l(mu); quit = true; }
-            cv.notify_all();
-            worker.join();
-        }
-    }
-};
-
-struct GvdState {
-    DedupScratch dedup;
-    DevBuf seeds, merge_state, hash_count, hash_start, hash_slot, hash_sorted, scan_tmp, misc;
-    DevBuf edges, bpts, near_idx, cand, cand_ok, skel, grid_bytes_ext;
-    PinnedBuf h_misc;
-    void *scratch = nullptr;   // GvdScratch (gvd.hip), freed by free_gvd_scratch
-    PinnedBuf h_seeds;   // seeds in / merged seeds out (g1)
-    PinnedBuf h_out;     // the GvdGraph arrays, gathered into it by one kernel (k_gather_words)
-    PinnedBuf h_evals;   // the graph searches' work counters (aos_params.gvd_count_evals)
-    aos_gvd_evals evals{};
-    SyncEvent sev;       // host waits of this state's GVD calls (the stream may be shared by several lanes)
-    Subdiv2D subdiv;   // host insert replay; kept across frames to reuse its allocations
-    // host outputs
-    std::vector<double> nodes_xy;
-    std::vector<int32_t> labels, cluster_idx, label_counts, label_clusters, label_types, edges_out;
-    std::vector<float> lengths, clearances;
-    int n_merged = 0, n_vor_edges = 0, n_bpts = 0;
-    int pairs_cap = 0;   // capacity of the g6 pair lists (from the last frame's pair count)
-    float ms_merge = 0, ms_delaunay = 0, ms_graph = 0, ms_total = 0;
-    // markers (aos_gvd_markers)
-    bool have_markers = false;
-    bool graph_ok = false;     // the last GVD call produced a graph (markers can be computed on demand)
-    int rect_mode = 0;         // its Subdiv2D rectangle mode
-    std::vector<double> merged_xy, row_label_xy;
-    std::vector<int32_t> row_label_valid;
-    std::unique_ptr<CellsWork> cells;   // the worker thread's own heap object (no false sharing)
-};
-
-struct GvdStageIn {
-    const double *seeds_host;  int n_seeds;     // /voronoi_seeds (x, y)
-    const double *rows_info;   int n_rows_poses;
-    aos_grid_info info;
-    const int8_t *d_skeleton;                   // framed skeleton bytes on device
-    // called once the merged seeds are on the host, when the GPU prefix is done and the host
-    // Subdiv2D replay starts (the pipelined caller lets the next seed-gen frame go from here)
-    void (*on_host_phase)(void *) = nullptr;
-    void *hook_arg = nullptr;
-};
-bool run_gvd_stage(GvdState &G, const aos_params &P, const GvdStageIn &in, hipStream_t stream, hipEvent_t *ev);
-void free_gvd_scratch(GvdState &G);
-// Joins the markers' cells job of the last GVD call; rethrow: raise its error (else discard it).
-void markers_wait(GvdState &G, bool rethrow);
-// aos_gvd_markers_get on a frame whose GVD ran without markers: compute them now (and wait)
-void markers_on_demand(GvdState &G);
 
 }  // namespace aos

@@ -987,7 +987,7 @@ void run_cluster_seed_stage(ClusterSeedState &S, const SeedStageIn &in, SeedStag
     const size_t ncand = (size_t)nslots + 8 * (size_t)nr;
     double2 *d_cand = dev<double2>(S.cand_xy, ncand), *d_rcand = d_cand + nslots, *d_ecand = d_rcand + 6 * nr;
     int *d_ok = dev<int>(S.cand_ok, ncand), *d_rok = d_ok + nslots, *d_eok = d_rok + 6 * nr;
-    double2 *d_vout = dev<double2>(S.hash_sorted, ncand), *d_rout = d_vout + nslots, *d_eout = d_rout + 6 * nr;
+    double2 *d_vout = dev<double2>(S.cand_kept, ncand), *d_rout = d_vout + nslots, *d_eout = d_rout + 6 * nr;
     double2 *d_seeds = dev<double2>(S.seed_out, ncand);
     int *d_cnt = dev<int>(S.misc, 8);   // kept counts: virtual, ray, endpoint
     const double hx0 = g.minx - 50.0, hx1 = g.maxx + 50.0, hy0 = g.miny - 50.0, hy1 = g.maxy + 50.0;

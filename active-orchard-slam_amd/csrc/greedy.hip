@@ -586,18 +586,6 @@ void dedup_check(DedupScratch &S, int err_word) {
     throw std::runtime_error("greedy de-duplication: device wait failed (error word " + std::to_string(err_word) + ")");
 }
 
-int greedy_dedup(DedupScratch &S, const double2 *cand, const int *ok, int n, int mode, double thr, const HashG &h,
-                 double2 *out, int *kept_index_out, hipStream_t s, int *h_scalar) {
-    if (n <= 0) return 0;
-    int *d = dev<int>(S.misc, 2);
-    greedy_dedup_async(S, cand, ok, n, mode, thr, h, out, kept_index_out, nullptr, d, s);
-    AOS_HIP(hipMemcpyAsync(h_scalar, d, sizeof(int), hipMemcpyDeviceToHost, s));
-    AOS_HIP(hipMemcpyAsync(h_scalar + 1, dedup_err(S, s), sizeof(int), hipMemcpyDeviceToHost, s));
-    S.sev.sync(s);
-    dedup_check(S, h_scalar[1]);
-    return h_scalar[0];
-}
-
 void greedy_dedup_small(DedupScratch &S, SmallDedup A, int nprob, hipStream_t s) {
     if (nprob <= 0) return;
     for (int k = 0; k < nprob; ++k)

@@ -9,21 +9,34 @@
 //  g7 filterNodesAndEdgesOutsideGrid          GPU  compaction
 //  g8 TL/TR/BL/BR label points                GPU  per (row, label) arg-min / castRay
 //  g9 publishGraph labels                     GPU  per node
+// This file: the stage's constants, every kernel, and run_gvd_stage with its steps. The markers' cells (host worker
+// thread): gvd_markers.hip. The handle's methods and the pipelined lanes: gvd_handle.hip. Declarations: gvd.h.
 #include <algorithm>
 #include <chrono>
 #include <cfloat>
 #include <climits>
 #include <cmath>
 #include <cstring>
-#include <exception>
-#include <limits>
-#include <thread>
+#include <stdexcept>
+#include <vector>
 
-#include "aos_ctx.h"
 #include "dev_prims_device.h"
-#include "subdiv2d.h"
+#include "gvd.h"
 
 namespace aos {
+
+// The stage's numbers (tests/gvd_scenes.py restates them for its predictors; tests/test_gvd_scenes_cpu.py pins them here)
+constexpr double kMergeRadius = 0.5;   // g1: seeds within <= 0.5 m merge (gvd:107-115); the merge index's cell
+constexpr double kMergeRange = 60.0;   // g1's cell index spans the grid +- 60 m (points beyond: border cells)
+constexpr double kBpCell = 0.5;        // g5's cell index, reused by g6: cells of 0.5 m (>= kPairMax) ...
+constexpr double kBpRange = 10.0;      // ... over the grid +- 10 m
+constexpr double kBpThr = 0.05;        // g5: ends with the same 1 cm key or nearer than 5 cm are one boundary point
+constexpr double kNodeCell = 5.01;     // g8's node index: cells of 5.01 m (k_label_points' pass 0 reads 3 x 3 of them) ...
+constexpr double kNodeRange = 10.0;    // ... over the grid +- 10 m
+constexpr double kLabelCell = 0.1;     // g9's label point index: cells of 0.1 m (a node's matches lie in 3 x 3) ...
+constexpr double kLabelRange = 1.0;    // ... over the grid +- 1 m
+constexpr int kPairCapMin = 1024;      // g6: the pair lists hold at least this many pairs
+constexpr double kPairMin = 1e-6, kPairMax = 0.5;   // g6 pairs: kPairMin < |bp_i - bp_j| <= kPairMax (gvd:861-894)
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 template <class T> static T *dev(DevBuf &b, size_t n) { return static_cast<T *>(b.ensure(sizeof(T) * std::max<size_t>(n, 1))); }
@@ -118,7 +131,7 @@ __global__ void k_nearest(const double2 *occ, int n_occ, CellIdx ci, const int *
             return true;
         });
     }
-    if (!(best < 0.05)) {  // safety net: exact brute force
+    if (!(best < kBpThr)) {  // safety net: exact brute force
         const int M = *M_dev;
         best = 1.7976931348623157e308; bi = -1;
         for (int i = 0; i < M; ++i) {
@@ -151,7 +164,7 @@ __device__ __forceinline__ int pairs_of(int i, const double2 *bp, CellIdx ci, co
             const int j = v.j;
             if (j <= i) return true;
             double dx = p.x - v.q.x, dy = p.y - v.q.y, d = sqrt(dx * dx + dy * dy);
-            if (d <= 0.5 && d > 1e-6) {
+            if (d <= kPairMax && d > kPairMin) {
                 if (!COUNT && w + c < cap) {  // insertion into the sorted run
                     int pos = w + c;
                     while (pos > w && plist[pos - 1].y > j) { plist[pos] = plist[pos - 1]; --pos; }
@@ -705,24 +718,20 @@ __global__ void k_facet_emit(const int *qe, const int *vfirst, const int *off, c
 
 // ------------------------------------------------------------------ orchestration
 struct GvdScratch {
-    DevBuf raw, ok, leaders, merged, owner, oidx, sowner, sidx, tmp, edges_f, occ, occ_ok, bp, kept_occ, keys, idx, skeys,
-        sidx2, near_idx, pk, pidx, pskeys, psidx, pcount, poff, plist, ft, ckey, cvalid, pass, k2, occ_idx, sk2, socc, selected,
-        inside, ipos, nodes, keep, kpos, edges, lens, jobs, nkeys, nidx, qkeys, qidx, lpts, lval, lmask, lcidx, lcount, loff, lcl, lty, scan_tmp,
-        misc, gcnt, goff, glist, evals;
+    DevBuf raw, leaders, merged, owner, misc;                       // g1 (misc: the stage's device scalars)
+    DevBuf occ, bp, pos_of;                                         // g5: edge ends, boundary points, ends -> points
+    DevBuf pcount, poff, ft, pass, grank, selected, gcnt, goff, glist;   // g6
+    DevBuf inside, ipos, nodes, keep, kpos, edges, lens;            // g7
+    DevBuf jobs, lpts, lval, lmask, lcidx, lcount, loff, lcl, lty;  // g8 / g9
+    DevBuf evals;
     bool gcnt_dirty = true;           // gcnt (edge groups' counts) not known to be zero
     CellScratch ci_nodes, ci_labels;  // g8 / g9 indices (g5 / g6 use the de-duplication's own)
     CellIdx cq{};
     LookBackScratch lb;               // the graph's single-pass scans
     FacetBufs fb;
 };
-static GvdScratch &scratch(GvdState &G) {
-    if (!G.scratch) G.scratch = new GvdScratch();
-    return *static_cast<GvdScratch *>(G.scratch);
-}
-void free_gvd_scratch(GvdState &G) {
-    delete static_cast<GvdScratch *>(G.scratch);   // DevBuf members free themselves
-    G.scratch = nullptr;
-}
+GvdState::GvdState() = default;
+GvdState::~GvdState() = default;   // (frees the scratch: every member frees itself)
 
 // Facets of a replayed Subdiv2D on the GPU: uploads the quad-edge state, computes every face's
 // circumcentre (k_vor_faces) and the per-vertex facet sizes (k_facet_count, 0 below 2 points), and
@@ -773,146 +782,283 @@ static void facets_emit(FacetBufs &F, const Subdiv2D::Raw &R, float4 *edges, hip
                                                               F.face.as<float2>(), edges, nullptr);
 }
 
-// publishMarkers' Voronoi cells (gvd:1098-1194): VoronoiDiagram::extractCellBoundaries
-// (voronoi_diagram.cpp:209-311), a second Subdiv2D over the finite merged seeds with their own
-// bounding box as the rectangle, then cell i = facet i (i < seeds, facets) with >= 3 points, closed
-// when its ends are more than 1 cm apart, paired with seeds_[i] and coloured from hue = i / cells.
-// Pure host work on the merged seeds: it runs on a worker thread next to the main replay.
-static void cells_colours(CellsWork &W, const std::vector<double> &seeds, int ncell);
-
-static void compute_cells(CellsWork &W, int rect_mode) {
-    const auto t0 = std::chrono::steady_clock::now();
-    struct CellTrace {
-        const double t = trace_on() ? trace_ms() : 0.0;
-        ~CellTrace() { if (trace_on()) fprintf(stderr, "[aos trace cells] %.2f -> %.2f\n", t, trace_ms()); }
-    } ctr;
-    W.cell_off.assign(1, 0);
-    W.cell_xy.clear(); W.cell_center.clear(); W.cell_rgba.clear();
-    const std::vector<double> &seeds = W.seeds;   // VoronoiDiagram::seeds_ = the finite merged seeds
-    const int ns = (int)seeds.size() / 2;
-    if (ns == 0) return;
-    double min_x = std::numeric_limits<double>::max(), max_x = std::numeric_limits<double>::lowest();
-    double min_y = min_x, max_y = max_x;
-    for (int i = 0; i < ns; ++i) {
-        min_x = std::min(min_x, seeds[2 * i]); max_x = std::max(max_x, seeds[2 * i]);
-        min_y = std::min(min_y, seeds[2 * i + 1]); max_y = std::max(max_y, seeds[2 * i + 1]);
-    }
-    if (max_x - min_x < 1.0) { double cx = (min_x + max_x) / 2.0; min_x = cx - 0.5; max_x = cx + 0.5; }
-    if (max_y - min_y < 1.0) { double cy = (min_y + max_y) / 2.0; min_y = cy - 0.5; max_y = cy + 0.5; }
+bool subdiv_build(Subdiv2D &sd, double min_x, double max_x, double min_y, double max_y, const double *xy, int n,
+                  int rect_mode) {
+    if (min_x > max_x) std::swap(min_x, max_x);
+    if (min_y > max_y) std::swap(min_y, max_y);
+    if (max_x - min_x < 1.0) { double c = (min_x + max_x) / 2.0; min_x = c - 0.5; max_x = c + 0.5; }
+    if (max_y - min_y < 1.0) { double c = (min_y + max_y) / 2.0; min_y = c - 0.5; max_y = c + 0.5; }
     const float rx = static_cast<float>(min_x - 1.0), ry = static_cast<float>(min_y - 1.0);
     const float rw = static_cast<float>(std::abs(max_x - min_x) + 2.0), rh = static_cast<float>(std::abs(max_y - min_y) + 2.0);
-    if (rw <= 0 || rh <= 0) return;
-    Subdiv2D &sd = W.sd;
-    sd.reserve(ns);
+    if (rw <= 0 || rh <= 0) return false;
+    sd.reserve(n);
     sd.init_delaunay(rx, ry, rw, rh, rect_mode);
     const float margin = 0.1f;
-    for (int i = 0; i < ns; ++i) {
-        float x = static_cast<float>(seeds[2 * i]), y = static_cast<float>(seeds[2 * i + 1]);
+    for (int i = 0; i < n; ++i) {
+        const double sx = xy[2 * i], sy = xy[2 * i + 1];
+        if (!std::isfinite(sx) || !std::isfinite(sy)) continue;
+        float x = static_cast<float>(sx), y = static_cast<float>(sy);
         x = std::max(rx + margin, std::min(rx + rw - margin, x));
         y = std::max(ry + margin, std::min(ry + rh - margin, y));
-        sd.insert(x, y);   // insertion failures are skipped (voronoi_diagram.cpp:280-285)
+        sd.insert(x, y);   // (a failed insertion is skipped, as the reference catches and goes on)
     }
-    // getVoronoiFacetList on the worker's own core (calcVoronoi + the facet walk of subdiv2d.cpp, the host
-    // reference of the main graph's GPU builder, bit-identical to it): the markers job needs no stream, pinned
-    // buffers or GPU time of its own; the walk costs the worker a few ms next to its replay. (The markers'
-    // facets on the GPU builder were kept as AOS_MARKERS_GPU_FACETS=1, removed.)
-    std::vector<int> off;
-    std::vector<float> xy;
-    sd.voronoi_facets(off, xy);
-    int ncell = 0;
-    for (size_t f = 0; f + 1 < off.size() && (int)f < ns; ++f) {
-        const int b0 = off[f], n = off[f + 1] - b0;
-        if (n < 3) continue;
-        for (int j = 0; j < n; ++j) { W.cell_xy.push_back(xy[2 * (b0 + j)]); W.cell_xy.push_back(xy[2 * (b0 + j) + 1]); }
-        const double dx = (double)xy[2 * b0] - (double)xy[2 * (b0 + n - 1)];
-        const double dy = (double)xy[2 * b0 + 1] - (double)xy[2 * (b0 + n - 1) + 1];
-        if (std::sqrt(dx * dx + dy * dy) > 0.01) { W.cell_xy.push_back(xy[2 * b0]); W.cell_xy.push_back(xy[2 * b0 + 1]); }
-        W.cell_off.push_back((int32_t)(W.cell_xy.size() / 2));
-        ++ncell;
-    }
-    cells_colours(W, seeds, ncell);
-    W.ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return true;
 }
 
-// cell i's centre and colour (gvd:1117-1145, float arithmetic as written)
-static void cells_colours(CellsWork &W, const std::vector<double> &seeds, int ncell) {
-    for (int i = 0; i < ncell; ++i) {
-        W.cell_center.push_back(seeds[2 * i]); W.cell_center.push_back(seeds[2 * i + 1]);
-        float hue = static_cast<float>(i) / std::max(1.0f, static_cast<float>(ncell));
-        float saturation = 0.7f, value = 0.9f;
-        float cc = value * saturation;
-        float x = cc * (1.0f - std::abs(std::fmod(hue * 6.0f, 2.0f) - 1.0f));
-        float m = value - cc;
-        float r = 0.0f, g = 0.0f, b = 0.0f;
-        if (hue < 1.0f / 6.0f) { r = cc; g = x; b = 0.0f; }
-        else if (hue < 2.0f / 6.0f) { r = x; g = cc; b = 0.0f; }
-        else if (hue < 3.0f / 6.0f) { r = 0.0f; g = cc; b = x; }
-        else if (hue < 4.0f / 6.0f) { r = 0.0f; g = x; b = cc; }
-        else if (hue < 5.0f / 6.0f) { r = x; g = 0.0f; b = cc; }
-        else { r = cc; g = 0.0f; b = x; }
-        W.cell_rgba.push_back(r + m); W.cell_rgba.push_back(g + m); W.cell_rgba.push_back(b + m); W.cell_rgba.push_back(0.4f);
+// ---- the grid (GridG from aos_grid_info)
+static GridG make_grid(const aos_grid_info &info) {
+    GridG g{};
+    g.ox = info.origin_x; g.oy = info.origin_y; g.res = (double)info.resolution;
+    g.W = (int)info.width; g.H = (int)info.height;
+    g.minx = info.origin_x; g.maxx = g.minx + info.width * info.resolution;
+    g.miny = info.origin_y; g.maxy = g.miny + info.height * info.resolution;
+    double gw = info.width * info.resolution, gh = info.height * info.resolution;
+    g.diag2 = std::sqrt(gw * gw + gh * gh) * 2.0;
+    g.diag3 = std::sqrt(gw * gw + gh * gh) * 3.0;
+    g.step = info.resolution * 0.5;
+    if (g.step < 0.01) g.step = 0.01;
+    return g;
+}
+
+// ---- g1 merge: the merged seeds -> merged (x, y per seed) and S.merged; returns their number. One host wait.
+static int merge_seeds(GvdState &G, GvdScratch &S, const GridG &g, const GvdStageIn &in, int *h_sc, hipStream_t s,
+                       HostTrace &tr, std::vector<double> &merged) {
+    const int n = in.n_seeds;
+    double2 *d_raw = dev<double2>(S.raw, n);
+    // seeds in and merged seeds out through the state's pinned buffer (a pageable copy is staged by the
+    // runtime and, measured on the streaming map, could stall ~20 ms behind unrelated copy traffic)
+    double *h_seeds = static_cast<double *>(G.h_seeds.ensure(sizeof(double2) * (size_t)n));
+    std::memcpy(h_seeds, in.seeds_host, sizeof(double2) * (size_t)n);
+    AOS_HIP(hipMemcpyAsync(d_raw, h_seeds, sizeof(double2) * n, hipMemcpyHostToDevice, s));
+    tr.mark("h2d");
+    const HashG hm = make_hash_n(g.minx - kMergeRange, g.maxx + kMergeRange, g.miny - kMergeRange, g.maxy + kMergeRange,
+                                 kMergeRadius, n);
+    double2 *d_merged = dev<double2>(S.merged, n);
+    int *d_leaders = dev<int>(S.leaders, n), *d_owner = dev<int>(S.owner, n);
+    int *d_cnt = dev<int>(S.misc, 8);
+    // leaders (the kept seeds) -> d_merged, overwritten in leader order by their means
+    greedy_dedup_async(G.dedup, d_raw, nullptr, n, kConflictLessEq, kMergeRadius, hm, d_merged, d_leaders, d_owner, d_cnt, s);
+    // (the means and the count come back from the same launch: one host wait)
+    k_merge_members<<<cdiv(n, 128), 128, 0, s>>>(d_raw, G.dedup.ci, d_owner, d_leaders, d_cnt, d_merged,
+                                                 reinterpret_cast<double2 *>(h_seeds), h_sc, dedup_err(G.dedup, s));
+    G.sev.sync(s);
+    dedup_check(G.dedup, h_sc[1]);
+    tr.mark("merge");
+    const int nl = h_sc[0];
+    merged.resize(2 * (size_t)nl);
+    std::memcpy(merged.data(), h_seeds, sizeof(double2) * (size_t)nl);
+    return nl;
+}
+
+// ---- g3/g4 finite filter, bounds, Subdiv2D inserts (host replay) -> facets / Voronoi edges (GPU): returns their
+// number ne, their ends (g5's candidates) in d_occ; -1 where processGraph returns without a graph (non-finite bounds,
+// no finite seed: gvd:273-275). One host wait (facets_count).
+static int voronoi_edges(GvdState &G, GvdScratch &S, const GridG &g, const std::vector<double> &merged, int rect_mode,
+                         int *h_sc, hipStream_t s, HostTrace &tr, double2 *&d_occ) {
+    const int nl = (int)(merged.size() / 2);
+    if (!std::isfinite(g.minx) || !std::isfinite(g.maxx) || !std::isfinite(g.miny) || !std::isfinite(g.maxy)) return -1;
+    bool any_finite = false;
+    for (int i = 0; i < nl; ++i) any_finite |= std::isfinite(merged[2 * i]) && std::isfinite(merged[2 * i + 1]);
+    if (!any_finite) return -1;
+    // VoronoiDiagram::compute voronoi_diagram.cpp:27-89
+    if (!subdiv_build(G.subdiv, g.minx, g.maxx, g.miny, g.maxy, merged.data(), nl, rect_mode)) return 0;
+    tr.mark("inserts");
+    Subdiv2D::Raw R{};
+    const int ne = facets_count(S.fb, G.subdiv, R, h_sc, s, G.sev);
+    tr.mark("facets");
+    d_occ = dev<double2>(S.occ, 2 * (size_t)std::max(ne, 1));   // (g5's candidates: the edge ends)
+    if (ne) facets_emit(S.fb, R, nullptr, s, d_occ);
+    return ne;
+}
+
+// ---- the exploration rows' label jobs (gvd:130-150, 485-556), four per row
+static std::vector<LabelRow> label_jobs(const double *rows_info, int nrows) {
+    std::vector<LabelRow> jobs;
+    for (int r = 0; r < nrows; ++r) {
+        double sx = rows_info[4 * r], sy = rows_info[4 * r + 1], ex = rows_info[4 * r + 2], ey = rows_info[4 * r + 3];
+        if (sx > ex) { std::swap(sx, ex); std::swap(sy, ey); }
+        // castRay angle terms (gvd:574-581): +90 -> cos(a), sin(a); -90 -> cos(-a), sin(-a)
+        const double am = -90.0 * M_PI / 180.0, ap = 90.0 * M_PI / 180.0;
+        const double cm = std::cos(-am), sm = std::sin(-am), cp = std::cos(ap), sp = std::sin(ap);
+        jobs.push_back({sx, sy, ex, ey, -90.0, cm, sm});
+        jobs.push_back({sx, sy, ex, ey, 90.0, cp, sp});
+        jobs.push_back({ex, ey, sx, sy, -90.0, cm, sm});
+        jobs.push_back({ex, ey, sx, sy, 90.0, cp, sp});
     }
+    return jobs;
 }
 
-// The cells' worker thread. publishMarkers runs after publishGraph (gvd:310-313), so the graph is
-// returned as soon as it is ready and the cells finish in the background: aos_gvd_markers_get, the
-// next GVD call and release() join the job (markers_wait). An error of the job is raised by
-// aos_gvd_markers_get; a job nobody asked about is discarded by the next call.
-static void markers_start(GvdState &G, int rect_mode) {
-    if (!G.cells) G.cells.reset(new CellsWork());
-    CellsWork &W = *G.cells;
-    W.seeds.clear();
-    for (size_t i = 0; i + 1 < G.merged_xy.size(); i += 2)
-        if (std::isfinite(G.merged_xy[i]) && std::isfinite(G.merged_xy[i + 1])) {
-            W.seeds.push_back(G.merged_xy[i]); W.seeds.push_back(G.merged_xy[i + 1]);
-        }
-    if (!W.worker.joinable())
-        W.worker = std::thread([&W]() {
-            std::unique_lock<std::mutex> l(W.mu);
-            for (;;) {
-                W.cv.wait(l, [&W] { return W.busy || W.quit; });
-                if (W.quit) return;
-                l.unlock();
-                std::exception_ptr e;
-                try { compute_cells(W, W.rect_mode); } catch (...) { e = std::current_exception(); }
-                l.lock();
-                W.err = e;
-                W.busy = false;
-                W.cv.notify_all();
-            }
-        });
-    {
-        std::lock_guard<std::mutex> l(W.mu);
-        W.rect_mode = rect_mode;
-        W.err = nullptr;
-        W.busy = true;
+// What the steps after the Voronoi edges share: the sizes the host knows and the frame's device arrays.
+struct GraphFrame {
+    GridG g;
+    const int8_t *sk;                    // the framed skeleton
+    int ne, no, nrows, nj;               // Voronoi edges, their 2 ne ends; exploration rows, 4 label jobs each
+    double2 *occ, *bp; int *pos_of;      // g5: the ends (its candidates), the boundary points, ends -> points (-1: dropped)
+    const int *M; CellIdx cio;           // ... their number (on the device) and the cell index over the ends
+    int *poff;                           // g6: the pairs' offsets per boundary point, [no] = P
+    unsigned long long *evals;           // the searches' work counters (null: not counted)
+    LabelRow *jobs; double2 *lp; int *lv;   // g8: the label jobs, their points and validity
+    double2 *nodes; int *in, *ipos;      // g7: the filtered nodes, the inside flags and their scan ([no] = Mn)
+    int *mask, *cidx, *lcnt, *loff;      // g9 per node: label mask, first row, entries and their scan
+    int *edges; float *lens;             // the kept edges (set by each attempt)
+};
+struct GraphSizes { int M, P, Mn, Ne, n_entries; };   // an attempt's read-back: points, pairs, nodes, edges, entries
+
+// ---- g5 boundary points: the 2E edge ends, de-duplicated (1 cm key or < 5 cm) through a cell index of
+// cells >= 0.5 m, which g6 reuses for its nearest-point and pair searches (pos_of: ends -> points); g6's pair counts
+// and offsets, which no capacity bears on; the label jobs' upload and the arrays g7-g9 fill
+// (jobs: the caller's, a pageable upload's source stays alive until the stage's last wait)
+static void graph_begin(GvdState &G, GvdScratch &S, GraphFrame &F, const double *rows_info, std::vector<LabelRow> &jobs,
+                        bool count_evals, hipStream_t s) {
+    const GridG &g = F.g;
+    const int no = F.no, nj = F.nj;
+    const HashG h5 = make_hash_n(g.minx - kBpRange, g.maxx + kBpRange, g.miny - kBpRange, g.maxy + kBpRange, kBpCell, no);
+    F.bp = dev<double2>(S.bp, no);
+    F.pos_of = dev<int>(S.pos_of, no);
+    int *d_sc = dev<int>(S.misc, 16);   // [0] M
+    greedy_dedup_async(G.dedup, F.occ, nullptr, no, kConflictKeyOrSq, kBpThr * kBpThr, h5, F.bp, nullptr, nullptr, d_sc, s,
+                       F.pos_of);
+    F.cio = G.dedup.ci;
+    F.M = d_sc;
+    if (count_evals) {   // (aos_params.gvd_count_evals)
+        F.evals = dev<unsigned long long>(S.evals, 8);
+        AOS_HIP(hipMemsetAsync(F.evals, 0, 8 * sizeof(unsigned long long), s));
     }
-    W.cv.notify_all();
+    int *d_pcount = dev<int>(S.pcount, no);
+    F.poff = dev<int>(S.poff, no + 1);
+    k_pairs_count<<<cdiv(no, 256), 256, 0, s>>>(F.bp, no, F.M, F.cio, F.pos_of, F.occ, d_pcount, F.evals);
+    scan_1p(S.lb, d_pcount, F.poff, no, false, s);
+    jobs = label_jobs(rows_info, F.nrows);
+    F.jobs = dev<LabelRow>(S.jobs, nj);
+    if (nj) AOS_HIP(hipMemcpyAsync(F.jobs, jobs.data(), sizeof(LabelRow) * nj, hipMemcpyHostToDevice, s));
+    F.lp = dev<double2>(S.lpts, nj);
+    F.lv = dev<int>(S.lval, nj);
+    F.nodes = dev<double2>(S.nodes, no);
+    F.in = dev<int>(S.inside, no); F.ipos = dev<int>(S.ipos, no + 1);
+    F.mask = dev<int>(S.lmask, no); F.cidx = dev<int>(S.lcidx, no); F.lcnt = dev<int>(S.lcount, no);
+    F.loff = dev<int>(S.loff, no + 1);
 }
 
-void markers_on_demand(GvdState &G) {
-    markers_start(G, G.rect_mode);
-    markers_wait(G, true);
-    G.have_markers = true;
-}
+// ---- one attempt of g5's nearest points to g9's counts with pair lists of capacity cap; returns the frame's sizes
+// (P > cap: the lists overflowed and the caller runs it again). One host wait.
+static GraphSizes graph_attempt(GvdState &G, GvdScratch &S, GraphFrame &F, int cap, unsigned long long *ev_k, int *h_sz,
+                                hipStream_t s) {
+    const GridG &g = F.g;
+    const int ne = F.ne, no = F.no, nj = F.nj, ncap = ne + cap;
+    int2 *d_ft = dev<int2>(S.ft, ncap);
+    // (round 5 measured k_nearest on a second stream beside the pair count, scan and lists: no gain, r05l)
+    k_nearest<<<cdiv(no, 256), 256, 0, s>>>(F.occ, no, F.cio, F.pos_of, F.bp, F.M, reinterpret_cast<int *>(d_ft), ev_k);
+    k_pairs<<<cdiv(no, 256), 256, 0, s>>>(F.bp, no, F.M, F.cio, F.pos_of, F.occ, F.poff, d_ft + ne, cap, ev_k);
+    int *d_pass = dev<int>(S.pass, ncap), *d_grank = dev<int>(S.grank, ncap), *d_sel = dev<int>(S.selected, ncap);
+    const size_t gc0 = S.gcnt.cap;
+    int *d_gcnt = dev<int>(S.gcnt, no);
+    if (S.gcnt.cap != gc0 || S.gcnt_dirty) AOS_HIP(hipMemsetAsync(d_gcnt, 0, S.gcnt.cap, s));
+    S.gcnt_dirty = true;
+    int *d_goff = dev<int>(S.goff, no + 1), *d_glist = dev<int>(S.glist, ncap);
+    k_occupancy<<<cdiv(ncap, kOccTB), kOccTB, 0, s>>>(d_ft, F.poff, no, ne, cap, F.bp, F.sk, g, d_pass, d_gcnt, d_grank, ev_k);
+    scan_1p(S.lb, d_gcnt, d_goff, no, true, s);   // (leaves the group counts zero)
+    S.gcnt_dirty = false;
+    k_group_scatter<<<cdiv(ncap, 256), 256, 0, s>>>(d_ft, d_pass, F.poff, no, ne, cap, d_goff, d_grank, d_glist);
+    k_select<<<cdiv(ncap, 256), 256, 0, s>>>(d_ft, d_pass, F.poff, no, ne, cap, d_goff, d_glist, d_sel);
 
-void markers_wait(GvdState &G, bool rethrow) {
-    if (!G.cells) return;
-    CellsWork &W = *G.cells;
-    std::unique_lock<std::mutex> l(W.mu);
-    W.cv.wait(l, [&W] { return !W.busy; });
-    if (W.err) {
-        std::exception_ptr e = W.err;
-        W.err = nullptr;
-        G.have_markers = false;
-        if (rethrow) std::rethrow_exception(e);
+    // ---- g7 filter
+    k_inside<<<cdiv(no, 256), 256, 0, s>>>(F.bp, no, F.M, g, F.in);
+    scan_1p(S.lb, F.in, F.ipos, no, false, s);
+    int *d_keep = dev<int>(S.keep, ncap), *d_kpos = dev<int>(S.kpos, ncap + 1);
+    k_edge_keep<<<cdiv(std::max(ncap, no), 256), 256, 0, s>>>(d_sel, d_ft, ncap, F.in, F.ipos, d_keep, F.bp, no, F.nodes);
+    scan_1p(S.lb, d_keep, d_kpos, ncap, false, s);
+    F.edges = dev<int>(S.edges, 2 * (size_t)ncap);
+    F.lens = dev<float>(S.lens, ncap);
+    k_edge_emit<<<cdiv(ncap, 256), 256, 0, s>>>(d_keep, d_kpos, d_ft, ncap, F.ipos, F.nodes, F.edges, F.lens);
+    const int *d_Mn = F.ipos + no;
+
+    // ---- g8 label points for the exploration rows: the nodes in cells of >= 5.01 m
+    if (nj) {
+        const HashG hl = make_hash_n(g.minx - kNodeRange, g.maxx + kNodeRange, g.miny - kNodeRange, g.maxy + kNodeRange,
+                                     kNodeCell, no);
+        const CellIdx cn = cell_index_build(S.ci_nodes, F.nodes, nullptr, no, hl, s, d_Mn);
+        k_label_points<<<nj, 256, 0, s>>>(F.jobs, nj, F.nodes, d_Mn, g, F.sk, cn, F.lp, F.lv, ev_k);
     }
+    // ---- g9 node labels: the valid label points in cells of >= 0.1 m
+    const HashG hq = make_hash_n(g.minx - kLabelRange, g.maxx + kLabelRange, g.miny - kLabelRange, g.maxy + kLabelRange,
+                                 kLabelCell, nj);
+    const CellIdx cq = S.cq = cell_index_build(S.ci_labels, F.lp, F.lv, nj, hq, s);
+    k_node_labels_count<<<cdiv(no, 256), 256, 0, s>>>(F.nodes, no, d_Mn, F.lp, F.lv, F.nrows, cq, F.mask, F.cidx, F.lcnt);
+    scan_1p(S.lb, F.lcnt, F.loff, no, false, s);
+    // the frame's sizes and error words: one read-back
+    peek_to_host(h_sz, {F.M, F.poff + no, d_Mn, d_kpos + ncap, F.loff + no, dedup_err(G.dedup, s), S.lb.err_word(s),
+                        S.ci_nodes.lb.err_word(s)}, s);
+    G.sev.sync(s);
+    if (h_sz[5] || h_sz[6] || h_sz[7]) {
+        if (h_sz[6] || h_sz[7]) throw std::runtime_error("GVD graph: single-pass scan failed on the device");
+        dedup_check(G.dedup, h_sz[5]);
+    }
+    return GraphSizes{h_sz[0], h_sz[1], h_sz[2], h_sz[3], h_sz[4]};
 }
 
+// ---- outputs: g9's label entries, then one gather kernel straight into the state's pinned buffer, one host wait
+// (ev_out recorded before it) and host copies out into G's arrays; the work counters come back into G.h_evals with
+// them. Returns the label jobs published.
+static int gather_outputs(GvdState &G, GvdScratch &S, const GraphFrame &F, const GraphSizes &z, hipStream_t s,
+                          hipEvent_t ev_out, HostTrace &tr) {
+    const int Mn = z.Mn, Ne = z.Ne, n_entries = z.n_entries;
+    const int nj_out = Mn > 0 ? F.nj : 0;   // (no nodes: no label jobs, gvd:485-556 finds nothing to label)
+    int *d_lcl = dev<int>(S.lcl, n_entries);
+    int *d_lty = dev<int>(S.lty, n_entries);
+    if (n_entries)
+        k_node_labels_fill<<<cdiv(Mn, 256), 256, 0, s>>>(F.nodes, Mn, F.lp, F.lv, F.nrows, S.cq, F.loff, d_lcl, d_lty);
+
+    G.nodes_xy.resize(2 * (size_t)Mn); G.labels.resize(Mn); G.cluster_idx.resize(Mn); G.label_counts.resize(Mn);
+    G.label_clusters.resize(n_entries); G.label_types.resize(n_entries);
+    G.edges_out.resize(2 * (size_t)Ne); G.lengths.resize(Ne); G.clearances.assign(Ne, 0.0f);
+    G.row_label_xy.resize(2 * (size_t)nj_out); G.row_label_valid.resize(nj_out);
+    struct Out { const void *d; void *h; long long words; };
+    const Out outs[] = {{F.nodes, G.nodes_xy.data(), 4LL * Mn}, {F.mask, G.labels.data(), Mn}, {F.cidx, G.cluster_idx.data(), Mn},
+                        {F.lcnt, G.label_counts.data(), Mn}, {d_lcl, G.label_clusters.data(), n_entries},
+                        {d_lty, G.label_types.data(), n_entries}, {F.edges, G.edges_out.data(), 2LL * Ne},
+                        {F.lens, G.lengths.data(), Ne}, {F.lp, G.row_label_xy.data(), 4LL * nj_out},
+                        {F.lv, G.row_label_valid.data(), nj_out}};
+    SegList sl{};
+    for (const Out &o : outs) {
+        if (o.words <= 0) continue;
+        sl.src[sl.n] = static_cast<const int *>(o.d);
+        sl.off[sl.n + 1] = sl.off[sl.n] + o.words;
+        ++sl.n;
+    }
+    const long long total = sl.off[sl.n];
+    int *h_out = static_cast<int *>(G.h_out.ensure(sizeof(int) * (size_t)std::max(total, 1LL)));
+    if (total) k_gather_words<<<cdiv(cdiv(total, 4), 256), 256, 0, s>>>(sl, h_out);   // (straight into the pinned buffer)
+    if (F.evals)
+        AOS_HIP(hipMemcpyAsync(G.h_evals.ensure(8 * sizeof(unsigned long long)), F.evals, 8 * sizeof(unsigned long long),
+                               hipMemcpyDeviceToHost, s));
+    AOS_HIP(hipEventRecord(ev_out, s));
+    G.sev.sync(s);
+    tr.mark("out");
+    for (const Out &o : outs)
+        if (o.words > 0) { std::memcpy(o.h, h_out, sizeof(int) * (size_t)o.words); h_out += o.words; }
+    return nj_out;
+}
+
+// ---- the work of the searches (SURVEY §8d "pair evaluations"), the reference's beside the GPU's
+static void fill_evals(GvdState &G, const GraphFrame &F, const GraphSizes &z, int nj_out) {
+    G.evals = aos_gvd_evals{};
+    if (!F.evals) return;
+    const unsigned long long *h_ev = G.h_evals.as<unsigned long long>();
+    aos_gvd_evals &E = G.evals;
+    const uint64_t M = (uint64_t)z.M;
+    E.counted = 1;
+    E.n_label_jobs = nj_out;
+    E.edge_ends = (uint64_t)F.no; E.boundary_points = M; E.filtered_nodes = (uint64_t)z.Mn;
+    E.ref_nearest = (uint64_t)F.no * M;                        // gvd:812-824 per edge end, every boundary point
+    E.ref_pairs = M ? M * (M - 1) / 2 : 0;                     // gvd:861-894
+    E.ref_labels = nj_out ? h_ev[4] * (uint64_t)z.Mn : 0;      // gvd:731-774, once per radius tried
+    E.gpu_nearest = h_ev[0]; E.gpu_pairs = h_ev[1]; E.gpu_samples = h_ev[2]; E.gpu_labels = h_ev[3];
+}
 
 bool run_gvd_stage(GvdState &G, const aos_params &P, const GvdStageIn &in, hipStream_t s, hipEvent_t *ev) {
     HostTrace tr{"gvd"};
-    GvdScratch &S = scratch(G);
+    if (!G.scratch) G.scratch.reset(new GvdScratch());
+    GvdScratch &S = *G.scratch;
     G.nodes_xy.clear(); G.labels.clear(); G.cluster_idx.clear(); G.label_counts.clear();
     G.label_clusters.clear(); G.label_types.clear(); G.edges_out.clear(); G.lengths.clear(); G.clearances.clear();
     G.n_merged = G.n_vor_edges = G.n_bpts = 0;
@@ -925,257 +1071,54 @@ bool run_gvd_stage(GvdState &G, const aos_params &P, const GvdStageIn &in, hipSt
     G.merged_xy.clear(); G.row_label_xy.clear(); G.row_label_valid.clear();
     if (G.cells) { G.cells->cell_off.assign(1, 0); G.cells->ms = 0; }
     int *h_sc = static_cast<int *>(G.h_misc.ensure(4096));
-    const int n = in.n_seeds;
     AOS_HIP(hipEventRecord(ev[6], s));
-    if (n <= 0) return false;  // processGraph: voronoi_seeds_.empty() -> return (gvd:257)
+    if (in.n_seeds <= 0) return false;  // processGraph: voronoi_seeds_.empty() -> return (gvd:257)
 
-    GridG g{};
-    g.ox = in.info.origin_x; g.oy = in.info.origin_y; g.res = (double)in.info.resolution;
-    g.W = (int)in.info.width; g.H = (int)in.info.height;
-    g.minx = in.info.origin_x; g.maxx = g.minx + in.info.width * in.info.resolution;
-    g.miny = in.info.origin_y; g.maxy = g.miny + in.info.height * in.info.resolution;
-    {
-        double gw = in.info.width * in.info.resolution, gh = in.info.height * in.info.resolution;
-        g.diag2 = std::sqrt(gw * gw + gh * gh) * 2.0;
-        g.diag3 = std::sqrt(gw * gw + gh * gh) * 3.0;
-        g.step = in.info.resolution * 0.5;
-        if (g.step < 0.01) g.step = 0.01;
-    }
+    GraphFrame F{};
+    F.g = make_grid(in.info);
+    F.sk = in.d_skeleton;
 
-    // ---- g1 merge
-    double2 *d_raw = dev<double2>(S.raw, n);
-    // seeds in and merged seeds out through the state's pinned buffer (a pageable copy is staged by the
-    // runtime and, measured on the streaming map, could stall ~20 ms behind unrelated copy traffic)
-    double *h_seeds = static_cast<double *>(G.h_seeds.ensure(sizeof(double2) * (size_t)n));
-    std::memcpy(h_seeds, in.seeds_host, sizeof(double2) * (size_t)n);
-    AOS_HIP(hipMemcpyAsync(d_raw, h_seeds, sizeof(double2) * n, hipMemcpyHostToDevice, s));
-    tr.mark("h2d");
-    const HashG hm = make_hash_n(g.minx - 60.0, g.maxx + 60.0, g.miny - 60.0, g.maxy + 60.0, 0.5, n);
-    double2 *d_merged = dev<double2>(S.merged, n);
-    int *d_leaders = dev<int>(S.leaders, n), *d_owner = dev<int>(S.owner, n);
-    int *d_cnt = dev<int>(S.misc, 8);
-    // leaders (the kept seeds) -> d_merged, overwritten in leader order by their means
-    greedy_dedup_async(G.dedup, d_raw, nullptr, n, kConflictLessEq, 0.5, hm, d_merged, d_leaders, d_owner, d_cnt, s);
-    // (the means and the count come back from the same launch: one host wait)
-    k_merge_members<<<cdiv(n, 128), 128, 0, s>>>(d_raw, G.dedup.ci, d_owner, d_leaders, d_cnt, d_merged,
-                                                 reinterpret_cast<double2 *>(h_seeds), h_sc, dedup_err(G.dedup, s));
-    G.sev.sync(s);
-    dedup_check(G.dedup, h_sc[1]);
-    tr.mark("merge");
-    const int nl = h_sc[0];
-    std::vector<double> merged(2 * (size_t)nl);
-    std::memcpy(merged.data(), h_seeds, sizeof(double2) * (size_t)nl);
-    G.n_merged = nl;
+    std::vector<double> merged;
+    G.n_merged = merge_seeds(G, S, F.g, in, h_sc, s, tr, merged);
     AOS_HIP(hipEventRecord(ev[7], s));
     G.merged_xy = merged;
     if (P.gvd_markers) markers_start(G, P.subdiv_rect_mode);
     if (in.on_host_phase) in.on_host_phase(in.hook_arg);
 
-    // ---- g3/g4 finite filter, bounds, Subdiv2D inserts (host replay) -> facets / Voronoi edges (GPU)
     auto t0 = std::chrono::steady_clock::now();
-    int ne = 0;
-    double2 *d_occ = nullptr;
-    {
-        double min_x = g.minx, max_x = g.maxx, min_y = g.miny, max_y = g.maxy;
-        if (!std::isfinite(min_x) || !std::isfinite(max_x) || !std::isfinite(min_y) || !std::isfinite(max_y)) return false;
-        bool any_finite = false;
-        for (int i = 0; i < nl; ++i) any_finite |= std::isfinite(merged[2 * i]) && std::isfinite(merged[2 * i + 1]);
-        if (!any_finite) return false;  // gvd:273-275
-        // VoronoiDiagram::compute voronoi_diagram.cpp:27-89
-        if (min_x > max_x) std::swap(min_x, max_x);
-        if (min_y > max_y) std::swap(min_y, max_y);
-        if (max_x - min_x < 1.0) { double c = (min_x + max_x) / 2.0; min_x = c - 0.5; max_x = c + 0.5; }
-        if (max_y - min_y < 1.0) { double c = (min_y + max_y) / 2.0; min_y = c - 0.5; max_y = c + 0.5; }
-        float rx = static_cast<float>(min_x - 1.0), ry = static_cast<float>(min_y - 1.0);
-        float rw = static_cast<float>(std::abs(max_x - min_x) + 2.0), rh = static_cast<float>(std::abs(max_y - min_y) + 2.0);
-        if (!(rw <= 0 || rh <= 0)) {
-            Subdiv2D &sd = G.subdiv;
-            sd.reserve(nl);
-            sd.init_delaunay(rx, ry, rw, rh, P.subdiv_rect_mode);
-            const float margin = 0.1f;
-            for (int i = 0; i < nl; ++i) {
-                const double sx = merged[2 * i], sy = merged[2 * i + 1];
-                if (!std::isfinite(sx) || !std::isfinite(sy)) continue;
-                float x = static_cast<float>(sx), y = static_cast<float>(sy);
-                x = std::max(rx + margin, std::min(rx + rw - margin, x));
-                y = std::max(ry + margin, std::min(ry + rh - margin, y));
-                sd.insert(x, y);
-            }
-            tr.mark("inserts");
-            Subdiv2D::Raw R{};
-            ne = facets_count(S.fb, sd, R, h_sc, s, G.sev);
-            tr.mark("facets");
-            d_occ = dev<double2>(S.occ, 2 * (size_t)std::max(ne, 1));   // (g5's candidates: the edge ends)
-            if (ne) facets_emit(S.fb, R, nullptr, s, d_occ);
-        }
-    }
+    F.ne = voronoi_edges(G, S, F.g, merged, P.subdiv_rect_mode, h_sc, s, tr, F.occ);
+    if (F.ne < 0) return false;
     auto t1 = std::chrono::steady_clock::now();
     G.ms_delaunay = std::chrono::duration<float, std::milli>(t1 - t0).count();
-    G.n_vor_edges = ne;
+    G.n_vor_edges = F.ne;
     AOS_HIP(hipEventRecord(ev[8], s));
-    if (ne == 0) {   // no boundary points: an empty graph is still published
+    if (F.ne == 0) {   // no boundary points: an empty graph is still published
         G.have_markers = P.gvd_markers != 0;
         G.graph_ok = true;
         return true;
     }
 
-    // ---- g5 boundary points: the 2E edge ends, de-duplicated (1 cm key or < 5 cm) through a cell index of
-    // cells >= 0.5 m, which g6 reuses for its nearest-point and pair searches (pos_of: ends -> points)
-    const int no = 2 * ne;
-    const HashG h5 = make_hash_n(g.minx - 10.0, g.maxx + 10.0, g.miny - 10.0, g.maxy + 10.0, 0.5, no);
-    double2 *d_bp = dev<double2>(S.bp, no);
-    int *d_pos_of = dev<int>(S.kept_occ, no);
-    int *d_sc = dev<int>(S.misc, 16);   // [0] M
-    const double thr5 = 0.05 * 0.05;
-    greedy_dedup_async(G.dedup, d_occ, nullptr, no, kConflictKeyOrSq, thr5, h5, d_bp, nullptr, nullptr, d_sc, s, d_pos_of);
-    const CellIdx cio = G.dedup.ci;
-    const int *d_M = d_sc;
-
-    // ---- g6 graph edges
-    unsigned long long *d_evals = nullptr;   // (aos_params.gvd_count_evals)
-    if (P.gvd_count_evals) {
-        d_evals = dev<unsigned long long>(S.evals, 8);
-        AOS_HIP(hipMemsetAsync(d_evals, 0, 8 * sizeof(unsigned long long), s));
-    }
-    int *d_pcount = dev<int>(S.pcount, no), *d_poff = dev<int>(S.poff, no + 1);
-    // The pair lists get a capacity from the last frame (P is read back only with the frame's sizes below);
-    // a frame with more pairs runs the rest again with the exact size.
-    int cap = G.pairs_cap > 0 ? G.pairs_cap : std::max(1024, 2 * no);
-    k_pairs_count<<<cdiv(no, 256), 256, 0, s>>>(d_bp, no, d_M, cio, d_pos_of, d_occ, d_pcount, d_evals);
-    scan_1p(S.lb, d_pcount, d_poff, no, false, s);
-    int Mn = 0, Ne = 0, n_entries = 0;
-    const int nrows = in.n_rows_poses / 2;
-    const int nj = 4 * nrows;
+    F.no = 2 * F.ne;
+    F.nrows = in.n_rows_poses / 2;
+    F.nj = 4 * F.nrows;
     std::vector<LabelRow> jobs;
-    for (int r = 0; r < nrows; ++r) {   // the exploration rows' label jobs (gvd:130-150, 485-556)
-        double sx = in.rows_info[4 * r], sy = in.rows_info[4 * r + 1], ex = in.rows_info[4 * r + 2], ey = in.rows_info[4 * r + 3];
-        if (sx > ex) { std::swap(sx, ex); std::swap(sy, ey); }
-        // castRay angle terms (gvd:574-581): +90 -> cos(a), sin(a); -90 -> cos(-a), sin(-a)
-        const double am = -90.0 * M_PI / 180.0, ap = 90.0 * M_PI / 180.0;
-        const double cm = std::cos(-am), sm = std::sin(-am), cp = std::cos(ap), sp = std::sin(ap);
-        jobs.push_back({sx, sy, ex, ey, -90.0, cm, sm});
-        jobs.push_back({sx, sy, ex, ey, 90.0, cp, sp});
-        jobs.push_back({ex, ey, sx, sy, -90.0, cm, sm});
-        jobs.push_back({ex, ey, sx, sy, 90.0, cp, sp});
-    }
-    LabelRow *d_jobs = dev<LabelRow>(S.jobs, nj);
-    if (nj) AOS_HIP(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(LabelRow) * nj, hipMemcpyHostToDevice, s));
-    double2 *d_lp = dev<double2>(S.lpts, nj);
-    int *d_lv = dev<int>(S.lval, nj);
-    double2 *d_nodes = dev<double2>(S.nodes, no);
-    int *d_in = dev<int>(S.inside, no), *d_ipos = dev<int>(S.ipos, no + 1);
-    int *d_mask = dev<int>(S.lmask, no), *d_cidx = dev<int>(S.lcidx, no), *d_lcnt = dev<int>(S.lcount, no),
-        *d_loff = dev<int>(S.loff, no + 1);
-    int *d_edges = nullptr, *d_lcl = nullptr, *d_lty = nullptr;
-    float *d_lens = nullptr;
-    int *h_sz = h_sc + 8;
+    graph_begin(G, S, F, in.rows_info, jobs, P.gvd_count_evals != 0, s);
+    // The pair lists get a capacity from the last frame (P is read back only with the frame's sizes);
+    // a frame with more pairs runs the rest again with the exact size.
+    int cap = G.pairs_cap > 0 ? G.pairs_cap : std::max(kPairCapMin, 2 * F.no);
+    GraphSizes z{};
     for (int attempt = 0;; ++attempt) {
-        const int ncap = ne + cap;
-        int2 *d_ft = dev<int2>(S.ft, ncap);
-        unsigned long long *ev_k = attempt ? nullptr : d_evals;   // (a rerun with the exact pair capacity is not counted)
-        // (round 5 measured k_nearest on a second stream beside the pair count, scan and lists: no gain, r05l)
-        k_nearest<<<cdiv(no, 256), 256, 0, s>>>(d_occ, no, cio, d_pos_of, d_bp, d_M, reinterpret_cast<int *>(d_ft), ev_k);
-        k_pairs<<<cdiv(no, 256), 256, 0, s>>>(d_bp, no, d_M, cio, d_pos_of, d_occ, d_poff, d_ft + ne, cap, ev_k);
-        int *d_pass = dev<int>(S.pass, ncap), *d_grank = dev<int>(S.occ_idx, ncap), *d_sel = dev<int>(S.selected, ncap);
-        const size_t gc0 = S.gcnt.cap;
-        int *d_gcnt = dev<int>(S.gcnt, no);
-        if (S.gcnt.cap != gc0 || S.gcnt_dirty) AOS_HIP(hipMemsetAsync(d_gcnt, 0, S.gcnt.cap, s));
-        S.gcnt_dirty = true;
-        int *d_goff = dev<int>(S.goff, no + 1), *d_glist = dev<int>(S.glist, ncap);
-        k_occupancy<<<cdiv(ncap, kOccTB), kOccTB, 0, s>>>(d_ft, d_poff, no, ne, cap, d_bp, in.d_skeleton, g, d_pass, d_gcnt, d_grank,
-                                                  ev_k);
-        scan_1p(S.lb, d_gcnt, d_goff, no, true, s);   // (leaves the group counts zero)
-        S.gcnt_dirty = false;
-        k_group_scatter<<<cdiv(ncap, 256), 256, 0, s>>>(d_ft, d_pass, d_poff, no, ne, cap, d_goff, d_grank, d_glist);
-        k_select<<<cdiv(ncap, 256), 256, 0, s>>>(d_ft, d_pass, d_poff, no, ne, cap, d_goff, d_glist, d_sel);
-
-        // ---- g7 filter
-        k_inside<<<cdiv(no, 256), 256, 0, s>>>(d_bp, no, d_M, g, d_in);
-        scan_1p(S.lb, d_in, d_ipos, no, false, s);
-        int *d_keep = dev<int>(S.keep, ncap), *d_kpos = dev<int>(S.kpos, ncap + 1);
-        k_edge_keep<<<cdiv(std::max(ncap, no), 256), 256, 0, s>>>(d_sel, d_ft, ncap, d_in, d_ipos, d_keep, d_bp, no, d_nodes);
-        scan_1p(S.lb, d_keep, d_kpos, ncap, false, s);
-        d_edges = dev<int>(S.edges, 2 * (size_t)ncap);
-        d_lens = dev<float>(S.lens, ncap);
-        k_edge_emit<<<cdiv(ncap, 256), 256, 0, s>>>(d_keep, d_kpos, d_ft, ncap, d_ipos, d_nodes, d_edges, d_lens);
-        const int *d_Mn = d_ipos + no;
-
-        // ---- g8 label points for the exploration rows: the nodes in cells of >= 5.01 m
-        if (nj) {
-            const HashG hl = make_hash_n(g.minx - 10.0, g.maxx + 10.0, g.miny - 10.0, g.maxy + 10.0, 5.01, no);
-            const CellIdx cn = cell_index_build(S.ci_nodes, d_nodes, nullptr, no, hl, s, d_Mn);
-            k_label_points<<<nj, 256, 0, s>>>(d_jobs, nj, d_nodes, d_Mn, g, in.d_skeleton, cn, d_lp, d_lv, ev_k);
-        }
-        // ---- g9 node labels: the valid label points in cells of >= 0.1 m
-        const HashG hq = make_hash_n(g.minx - 1.0, g.maxx + 1.0, g.miny - 1.0, g.maxy + 1.0, 0.1, nj);
-        const CellIdx cq = S.cq = cell_index_build(S.ci_labels, d_lp, d_lv, nj, hq, s);
-        k_node_labels_count<<<cdiv(no, 256), 256, 0, s>>>(d_nodes, no, d_Mn, d_lp, d_lv, nrows, cq, d_mask, d_cidx, d_lcnt);
-        scan_1p(S.lb, d_lcnt, d_loff, no, false, s);
-        // the frame's sizes and error words: one read-back
-        peek_to_host(h_sz, {d_M, d_poff + no, d_Mn, d_kpos + ncap, d_loff + no, dedup_err(G.dedup, s), S.lb.err_word(s),
-                            S.ci_nodes.lb.err_word(s)}, s);
-        G.sev.sync(s);
-        if (h_sz[5] || h_sz[6] || h_sz[7]) {
-            if (h_sz[6] || h_sz[7]) throw std::runtime_error("GVD graph: single-pass scan failed on the device");
-            dedup_check(G.dedup, h_sz[5]);
-        }
-        const int P_ = h_sz[1];
-        G.pairs_cap = std::max(1024, P_ + P_ / 4);
-        if (P_ <= cap) {
-            G.n_bpts = h_sz[0];
-            Mn = h_sz[2]; Ne = h_sz[3]; n_entries = h_sz[4];
-            break;
-        }
+        // (a rerun with the exact pair capacity is not counted)
+        z = graph_attempt(G, S, F, cap, attempt ? nullptr : F.evals, h_sc + 8, s);
+        G.pairs_cap = std::max(kPairCapMin, z.P + z.P / 4);
+        if (z.P <= cap) break;
         if (attempt) throw std::runtime_error("GVD graph: pair lists overflowed twice");
         cap = G.pairs_cap;
     }
+    G.n_bpts = z.M;
     tr.mark("graph");
-    const int nj_out = Mn > 0 ? nj : 0;   // (no nodes: no label jobs, gvd:485-556 finds nothing to label)
-    d_lcl = dev<int>(S.lcl, n_entries);
-    d_lty = dev<int>(S.lty, n_entries);
-    if (n_entries)
-        k_node_labels_fill<<<cdiv(Mn, 256), 256, 0, s>>>(d_nodes, Mn, d_lp, d_lv, nrows, S.cq, d_loff, d_lcl, d_lty);
 
-    // ---- outputs: one gather kernel, one D2H copy into the state's pinned buffer, host copies out
-    G.nodes_xy.resize(2 * (size_t)Mn); G.labels.resize(Mn); G.cluster_idx.resize(Mn); G.label_counts.resize(Mn);
-    G.label_clusters.resize(n_entries); G.label_types.resize(n_entries);
-    G.edges_out.resize(2 * (size_t)Ne); G.lengths.resize(Ne); G.clearances.assign(Ne, 0.0f);
-    G.row_label_xy.resize(2 * (size_t)nj_out); G.row_label_valid.resize(nj_out);
-    struct Out { const void *d; void *h; long long words; };
-    const Out outs[] = {{d_nodes, G.nodes_xy.data(), 4LL * Mn}, {d_mask, G.labels.data(), Mn}, {d_cidx, G.cluster_idx.data(), Mn},
-                        {d_lcnt, G.label_counts.data(), Mn}, {d_lcl, G.label_clusters.data(), n_entries},
-                        {d_lty, G.label_types.data(), n_entries}, {d_edges, G.edges_out.data(), 2LL * Ne},
-                        {d_lens, G.lengths.data(), Ne}, {d_lp, G.row_label_xy.data(), 4LL * nj_out},
-                        {d_lv, G.row_label_valid.data(), nj_out}};
-    SegList sl{};
-    for (const Out &o : outs) {
-        if (o.words <= 0) continue;
-        sl.src[sl.n] = static_cast<const int *>(o.d);
-        sl.off[sl.n + 1] = sl.off[sl.n] + o.words;
-        ++sl.n;
-    }
-    const long long total = sl.off[sl.n];
-    int *h_out = static_cast<int *>(G.h_out.ensure(sizeof(int) * (size_t)std::max(total, 1LL)));
-    if (total) k_gather_words<<<cdiv(cdiv(total, 4), 256), 256, 0, s>>>(sl, h_out);   // (straight into the pinned buffer)
-    unsigned long long *h_ev = d_evals ? static_cast<unsigned long long *>(G.h_evals.ensure(8 * sizeof(unsigned long long))) : nullptr;
-    if (d_evals) AOS_HIP(hipMemcpyAsync(h_ev, d_evals, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    AOS_HIP(hipEventRecord(ev[9], s));
-    G.sev.sync(s);
-    tr.mark("out");
-    G.evals = aos_gvd_evals{};
-    if (h_ev) {   // the work of the searches (SURVEY §8d "pair evaluations"), the reference's beside the GPU's
-        aos_gvd_evals &E = G.evals;
-        const uint64_t M = (uint64_t)G.n_bpts;
-        E.counted = 1;
-        E.n_label_jobs = nj_out;
-        E.edge_ends = (uint64_t)no; E.boundary_points = M; E.filtered_nodes = (uint64_t)Mn;
-        E.ref_nearest = (uint64_t)no * M;                        // gvd:812-824 per edge end, every boundary point
-        E.ref_pairs = M ? M * (M - 1) / 2 : 0;                   // gvd:861-894
-        E.ref_labels = nj_out ? h_ev[4] * (uint64_t)Mn : 0;      // gvd:731-774, once per radius tried
-        E.gpu_nearest = h_ev[0]; E.gpu_pairs = h_ev[1]; E.gpu_samples = h_ev[2]; E.gpu_labels = h_ev[3];
-    }
-    for (const Out &o : outs)
-        if (o.words > 0) { std::memcpy(o.h, h_out, sizeof(int) * (size_t)o.words); h_out += o.words; }
+    fill_evals(G, F, z, gather_outputs(G, S, F, z, s, ev[9], tr));
     G.have_markers = P.gvd_markers != 0;
     G.graph_ok = true;
     float a = 0, b = 0;
@@ -1188,240 +1131,3 @@ bool run_gvd_stage(GvdState &G, const aos_params &P, const GvdStageIn &in, hipSt
 
 }  // namespace aos
 
-// ------------------------------------------------------------------ handle methods
-using namespace aos;
-
-static void fill_gvd_out(const aos_ctx &c, const GvdState &G, const aos_grid_info &info, bool published, aos_gvd_out &out) {
-    std::memset(&out, 0, sizeof(out));
-    out.published = published ? 1 : 0;
-    out.resolution = info.resolution;  // GvdGraph.resolution = skeleton info.resolution (gvd:903)
-    out.origin_x = info.origin_x; out.origin_y = info.origin_y;
-    out.num_nodes = (int32_t)G.labels.size();
-    out.num_edges = (int32_t)G.lengths.size();
-    out.nodes_xy = G.nodes_xy.data();
-    out.node_labels = G.labels.data(); out.node_cluster_indices = G.cluster_idx.data();
-    out.node_label_counts = G.label_counts.data();
-    out.n_label_entries = (int32_t)G.label_clusters.size();
-    out.node_label_clusters = G.label_clusters.data(); out.node_label_types = G.label_types.data();
-    out.edges = G.edges_out.data(); out.edge_lengths = G.lengths.data(); out.edge_clearances = G.clearances.data();
-    out.n_merged_seeds = G.n_merged; out.n_voronoi_edges = G.n_vor_edges; out.n_boundary_points = G.n_bpts;
-    out.ms_merge = G.ms_merge; out.ms_delaunay = G.ms_delaunay; out.ms_graph = G.ms_graph; out.ms_total = G.ms_total;
-    out.ms_cells = 0.0f;   // the cells job may still run: aos_gvd_markers.ms_cells
-    (void)c;
-}
-
-void aos_ctx::run_gvd_external(const aos_gvd_in &in, aos_gvd_out &out) {
-    gvd_async_drop();
-    GvdState &G = gs();
-    const size_t C = (size_t)in.info.width * in.info.height;
-    int8_t *d_sk = static_cast<int8_t *>(G.skel.ensure(std::max<size_t>(C, 1)));
-    if (C && in.skeleton) AOS_HIP(hipMemcpyAsync(d_sk, in.skeleton, C, hipMemcpyHostToDevice, stream));
-    GvdStageIn gi{in.seeds_xy, in.n_seeds, in.rows_info_xy, in.n_rows_poses, in.info, d_sk};
-    have_gvd = false;
-    const bool pub = run_gvd_stage(G, P, gi, stream, ev.data());
-    have_gvd = true; gvd_from_frame = false; gvd_skel = d_sk; gvd_info = in.info; ++gvd_gen;
-    fill_gvd_out(*this, G, in.info, pub, out);
-}
-
-void aos_ctx::run_gvd_from_frame(aos_gvd_out &out) {
-    gvd_async_drop();
-    GvdState &G = gs();
-    aos_grid_info info{geom.origin_x, geom.origin_y, geom.res, (uint32_t)geom.W, (uint32_t)geom.H};
-    GvdStageIn gi{h_voronoi.data(), (int)(h_voronoi.size() / 2), h_rows_info.data(), (int)(h_rows_info.size() / 2), info,
-                  skel_bytes.as<int8_t>()};
-    have_gvd = false;
-    const bool pub = run_gvd_stage(G, P, gi, stream, ev.data());
-    have_gvd = true; gvd_from_frame = true; gvd_frame_gen = frame_gen; gvd_skel = gi.d_skeleton; gvd_info = info; ++gvd_gen;
-    fill_gvd_out(*this, G, info, pub, out);
-}
-
-// ------------------------------------------------------------------ pipelined GVD
-// aos_gvd_from_seedgen_async: snapshot the frame's GVD inputs (host seeds and rows, a device copy of
-// the skeleton ordered on the seed-gen stream) into a free lane, whose worker runs the same
-// run_gvd_stage on the lane's stream. The next seed-gen frame may run meanwhile; it rewrites only
-// seed-gen state. Frames are independent, so with aos_gvd_pipeline_depth(D) up to D jobs run at once
-// (each Subdiv2D replay on its own host core); aos_gvd_wait collects them in start order.
-void aos_ctx::gvd_lanes_ensure() {
-    if (lanes.empty()) lanes.emplace_back(new GvdLane());
-    while ((int)lanes.size() < gvd_depth + 1) lanes.emplace_back(new GvdLane());
-}
-
-void aos_ctx::lane_join(int l) {
-    AsyncGvd &A = lanes[l]->ag;
-    if (!A.worker.joinable()) return;
-    std::unique_lock<std::mutex> lk(A.mu);
-    A.cv.wait(lk, [&A] { return !A.busy; });
-}
-
-void aos_ctx::lane_apply(int l) {
-    lanes[l]->ag.applied = true;
-    cur_lane = l;
-    have_gvd = true; gvd_from_frame = false; gvd_skel = lanes[l]->gs.skel.as<int8_t>(); gvd_info = lanes[l]->ag.info;
-    ++gvd_gen;
-}
-
-void aos_ctx::gvd_async_start() {
-    gvd_lanes_ensure();
-    // D jobs in flight already: the oldest is superseded (joined, its result dropped)
-    while ((int)inflight.size() >= gvd_depth) {
-        const int l = inflight.front();
-        inflight.pop_front();
-        lane_join(l);
-        std::lock_guard<std::mutex> lk(lanes[l]->ag.mu);
-        lanes[l]->ag.done = false;
-        lanes[l]->ag.err = nullptr;
-    }
-    int L = -1;   // a lane that holds neither the current result nor a job
-    for (int i = 0; i < (int)lanes.size() && L < 0; ++i)
-        if (i != cur_lane && std::find(inflight.begin(), inflight.end(), i) == inflight.end()) L = i;
-    if (L < 0) throw std::logic_error("gvd_async_start: no free lane");
-    GvdLane &ln = *lanes[L];
-    AsyncGvd &A = ln.ag;
-    if (!gvd_stream) AOS_HIP(hipStreamCreateWithFlags(&gvd_stream, hipStreamNonBlocking));
-    if (!A.stream) {
-        // every lane queues its GPU work on the handle's one GVD stream (few streams for the GPU's 4 hardware
-        // queues: no false dependencies behind unrelated streams); each lane waits on its own events
-        A.stream = gvd_stream;
-        for (auto &e : A.ev) AOS_HIP(hipEventCreate(&e));
-        AOS_HIP(hipEventCreateWithFlags(&A.ready, hipEventDisableTiming));
-    }
-    A.seeds = h_voronoi;
-    A.rows = h_rows_info;
-    A.P = P;   // snapshot on the caller's thread: aos_gvd_set_markers may change P while the job runs
-    A.applied = false;
-    A.info = aos_grid_info{geom.origin_x, geom.origin_y, geom.res, (uint32_t)geom.W, (uint32_t)geom.H};
-    const size_t C = (size_t)geom.W * geom.H;
-    int8_t *d_sk = static_cast<int8_t *>(ln.gs.skel.ensure(std::max<size_t>(C, 1)));
-    AOS_HIP(hipMemcpyAsync(d_sk, skel_bytes.p, C, hipMemcpyDeviceToDevice, stream));
-    AOS_HIP(hipEventRecord(A.ready, stream));
-    AOS_HIP(hipStreamWaitEvent(A.stream, A.ready, 0));
-    if (!A.worker.joinable())
-        A.worker = std::thread([this, &ln]() {
-            AsyncGvd &W = ln.ag;
-            std::unique_lock<std::mutex> l(W.mu);
-            for (;;) {
-                W.cv.wait(l, [&W] { return W.busy || W.quit; });
-                if (W.quit) return;
-                l.unlock();
-                std::exception_ptr e;
-                bool pub = false;
-                try {
-                    AOS_HIP(hipSetDevice(device));
-                    GvdStageIn gi{W.seeds.data(), (int)(W.seeds.size() / 2), W.rows.data(), (int)(W.rows.size() / 2),
-                                  W.info, ln.gs.skel.as<int8_t>()};
-                    gi.hook_arg = &W;
-                    gi.on_host_phase = [](void *p) {
-                        AsyncGvd *A = static_cast<AsyncGvd *>(p);
-                        { std::lock_guard<std::mutex> g(A->mu); A->prefix = true; }
-                        A->cv.notify_all();
-                    };
-                    pub = run_gvd_stage(ln.gs, W.P, gi, W.stream, W.ev.data());
-                } catch (...) { e = std::current_exception(); }
-                l.lock();
-                W.err = e;
-                W.pub = pub;
-                W.busy = false;
-                W.done = true;
-                W.cv.notify_all();
-            }
-        });
-    {
-        std::lock_guard<std::mutex> l(A.mu);
-        A.err = nullptr;
-        A.done = false;
-        A.prefix = false;
-        A.busy = true;
-    }
-    A.cv.notify_all();
-    inflight.push_back(L);
-    view_newest = true;
-    // Return once the job's short GPU prefix (seed merge) is done and its host replay runs: a
-    // seed-gen frame launched earlier would occupy the GPU and hold the prefix back, and the replay
-    // would start late instead of overlapping it.
-    std::unique_lock<std::mutex> l(A.mu);
-    A.cv.wait(l, [&A] { return A.prefix || !A.busy; });
-}
-
-// aos_gvd_wait: collects the oldest job in flight (raising its error if rethrow); its lane becomes
-// the handle's current result (markers, planning).
-bool aos_ctx::gvd_async_wait(bool rethrow) {
-    if (inflight.empty()) return false;
-    const int l = inflight.front();
-    inflight.pop_front();
-    view_newest = false;
-    lane_join(l);
-    AsyncGvd &A = lanes[l]->ag;
-    std::exception_ptr e;
-    {
-        std::lock_guard<std::mutex> lk(A.mu);
-        A.done = false;
-        e = A.err;
-        A.err = nullptr;
-    }
-    if (e) {
-        if (rethrow) std::rethrow_exception(e);
-        return false;
-    }
-    // a settle (markers / planning before this wait) already made this lane current: same graph, so the
-    // path planner's graph cache (keyed on gvd_gen) stays valid
-    if (!(cur_lane == l && A.applied && have_gvd)) lane_apply(l);
-    return true;
-}
-
-// Markers and planning on the handle's own graph: right after aos_gvd_wait they see the collected
-// job; with no wait since the last start they see the newest job (waited for, still collectable).
-void aos_ctx::gvd_view_settle() {
-    if (!view_newest || inflight.empty()) return;
-    const int l = inflight.back();
-    lane_join(l);
-    AsyncGvd &A = lanes[l]->ag;
-    bool ok;
-    {
-        std::lock_guard<std::mutex> lk(A.mu);
-        ok = A.done && !A.err;
-    }
-    if (ok && (cur_lane != l || !have_gvd)) lane_apply(l);
-}
-
-// A synchronous GVD call (or the handle's release) supersedes every job in flight.
-void aos_ctx::gvd_async_drop() {
-    gvd_lanes_ensure();
-    for (int l : inflight) {
-        lane_join(l);
-        std::lock_guard<std::mutex> lk(lanes[l]->ag.mu);
-        lanes[l]->ag.done = false;
-        lanes[l]->ag.err = nullptr;
-    }
-    inflight.clear();
-    view_newest = false;
-}
-
-void aos_ctx::gvd_async_stop() {
-    for (auto &lp : lanes) {
-        AsyncGvd &A = lp->ag;
-        if (A.worker.joinable()) {
-            { std::lock_guard<std::mutex> l(A.mu); A.quit = true; }
-            A.cv.notify_all();
-            A.worker.join();
-        }
-        if (A.stream) {
-            (void)hipStreamSynchronize(A.stream);
-            for (auto &e : A.ev) (void)hipEventDestroy(e);
-            (void)hipEventDestroy(A.ready);
-            A.stream = nullptr;   // (the shared gvd_stream)
-        }
-    }
-    if (gvd_stream) {
-        (void)hipStreamDestroy(gvd_stream);
-        gvd_stream = nullptr;
-    }
-    inflight.clear();
-    view_newest = false;
-}
-
-int aos::gvd_wait_out(aos_ctx *c, aos_gvd_out *out) {   // aos_gvd_wait (api.hip)
-    if (!c->gvd_async_wait(true)) return 0;
-    const aos_ctx::GvdLane &ln = *c->lanes[c->cur_lane];
-    fill_gvd_out(*c, ln.gs, ln.ag.info, ln.ag.pub, *out);
-    return 1;
-}

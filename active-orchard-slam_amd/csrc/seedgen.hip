@@ -19,11 +19,10 @@
 
 using namespace aos;
 
+// Teardown (aos_destroy): only what has an order or does not free itself. Every DevBuf, PinnedBuf and HostBuf member
+// (the lanes' GvdStates and their scratch included) goes with `delete`, in aos_destroy's device scope; no destructor
+// touches the handle's stream or events.
 void aos_ctx::release() {
-    for (DevBuf *b : {&cloud_copy, &bin_count, &bin_start, &sorted, &ror_scratch, &ror_bigbins, &scan_tmp, &counters,
-                      &raster_bits, &infl_bits, &open_bits, &thin_a, &thin_b, &thin_out, &thin_act, &occ_bytes, &skel_bytes, &flags,
-                      &full_infl, &full_skel, &map_buf, &scan_stage, &coll_red})
-        b->release();
     for (hipEvent_t e : coll_ev) (void)hipEventDestroy(e);
     coll_ev.clear();
     thin_graphs_release();
@@ -36,40 +35,16 @@ void aos_ctx::release() {
         (void)hipStreamDestroy(copy_stream);
         copy_stream = nullptr;
     }
-    h_small.release();
-    h_stats.release();
-    h_occ.release();
-    h_skel.release();
-    h_occ_bits.release();
-    h_skel_bits.release();
-    for (DevBuf *b : {&cs.fg_bits, &cs.word_cnt, &cs.word_off, &cs.fg_list, &cs.parent, &cs.root_flag, &cs.root_rank,
-                      &cs.cl_count, &cs.cl_off, &cs.cl_cursor, &cs.cl_cells, &cs.rec, &cs.row_idx, &cs.cur_tab,
-                      &cs.poly, &cs.cand_xy, &cs.cand_ok, &cs.cand_state, &cs.hash_count,
-                      &cs.hash_start, &cs.hash_slot, &cs.hash_sorted, &cs.seed_out, &cs.misc, &cs.scan_tmp})
-        b->release();
-    cs.h_misc.release();
     gvd_async_stop();   // joins the jobs in flight (they use the lanes' GvdStates)
     try { prefetch_join(); } catch (...) {}
     release_uploader();
-    for (CloudSplit *sp : {&split_cur, &split_next}) {
+    for (CloudSplit *sp : {&split_cur, &split_next})
         if (sp->copied) { (void)hipEventSynchronize(sp->copied); (void)hipEventDestroy(sp->copied); sp->copied = nullptr; }
-        sp->copy_pending = false;
-        sp->rest.release();
-        sp->on = false;
-    }
-    free_path_state(path_state);
+    free_path_state(path_state);   // (a void * owner: path.hip's PathState)
     path_state = nullptr;
-    have_gvd = false;
     for (auto &lp : lanes) {
-        GvdState &gs = lp->gs;
-        markers_wait(gs, false);
-        free_gvd_scratch(gs);
-        gs.cells.reset();
-        for (DevBuf *b : {&gs.seeds, &gs.merge_state, &gs.hash_count, &gs.hash_start, &gs.hash_slot, &gs.hash_sorted,
-                          &gs.scan_tmp, &gs.edges, &gs.bpts, &gs.near_idx, &gs.cand, &gs.cand_ok, &gs.skel,
-                          &gs.grid_bytes_ext})
-            b->release();
-        gs.h_misc.release();
+        markers_wait(lp->gs, false);
+        lp->gs.cells.reset();
     }
 }
 
@@ -270,7 +245,6 @@ void aos_ctx::release_uploader() {
             (void)hipStreamDestroy(up.st[t]);
             up.st[t] = nullptr;
         }
-        for (int k = 0; k < kUpSlots; ++k) { up.slot[t][k].release(); up.used[t][k] = false; }
     }
 }
 

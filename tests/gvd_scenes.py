@@ -18,25 +18,25 @@ RES = 0.25
 ORIGIN = (100.0, 200.0)
 
 # the library's constants the predictors use
-LF_TB = 256            # csrc/greedy.hip:309   kLfTB (candidates per k_lfmis block)
-LF_LIST = 16           # csrc/greedy.hip:309   kLfList (listed earlier conflicting candidates; more: the `over` re-walk)
-NODE_MATCH = 16        # csrc/gvd.hip:494      kNodeMatch (label points listed per node; more: the plain loop)
-NEAR_THREADS = 512     # csrc/path.hip:41      kNearThreads (k_nearest_k's one block)
-NEAR_K = 5             # csrc/path.hip:41      kNearK
-MERGE_R = 0.5          # csrc/gvd.hip:1001     g1: kConflictLessEq, d <= 0.5
-MERGE_RANGE = 60.0     # csrc/gvd.hip:996      g1's cell index spans the grid +- 60 m (points beyond: border cells)
-BP_CELL = 0.5          # csrc/gvd.hip:1068     g5's cell index: the grid +- 10 m in cells of 0.5 m
+LF_TB = 256            # csrc/greedy.hip       kLfTB (candidates per k_lfmis block)
+LF_LIST = 16           # csrc/greedy.hip       kLfList (listed earlier conflicting candidates; more: the `over` re-walk)
+NODE_MATCH = 16        # csrc/gvd.hip          kNodeMatch (label points listed per node; more: the plain loop)
+NEAR_THREADS = 512     # csrc/path.hip         kNearThreads (k_nearest_k's one block)
+NEAR_K = 5             # csrc/path.hip         kNearK
+MERGE_R = 0.5          # csrc/gvd.hip          kMergeRadius (merge_seeds, g1: kConflictLessEq, d <= 0.5)
+MERGE_RANGE = 60.0     # csrc/gvd.hip          kMergeRange: g1's cell index spans the grid +- 60 m (points beyond: border cells)
+BP_CELL = 0.5          # csrc/gvd.hip          kBpCell, kBpRange (graph_begin): g5's cell index: the grid +- 10 m in cells of 0.5 m
 BP_RANGE = 10.0
-BP_THR_SQ = 0.05 * 0.05   # csrc/gvd.hip:1072  g5: the same 1 cm key, or d^2 < 0.0025
-NODE_CELL = 5.01       # csrc/gvd.hip:1148     g8's node index: the grid +- 10 m in cells of 5.01 m
+BP_THR_SQ = 0.05 * 0.05   # csrc/gvd.hip       kBpThr squared, g5: the same 1 cm key, or d^2 < 0.0025
+NODE_CELL = 5.01       # csrc/gvd.hip          kNodeCell, kNodeRange (graph_attempt): g8's node index: the grid +- 10 m in cells of 5.01 m
 NODE_RANGE = 10.0
-LABEL_CELL = 0.1       # csrc/gvd.hip:1153     g9's label point index: the grid +- 1 m in cells of 0.1 m
+LABEL_CELL = 0.1       # csrc/gvd.hip          kLabelCell, kLabelRange (graph_attempt): g9's label point index: the grid +- 1 m in cells of 0.1 m
 LABEL_RANGE = 1.0
-CELLS_PER_ITEM = 2.0   # csrc/dev_prims.h:26    make_hash_n: at most max(HASH_MIN_CELLS, cells_per_item * n) cells
-HASH_MIN_CELLS = 4096  # csrc/greedy.hip:56
-HASH_GROW = 1.25       # csrc/greedy.hip:49    make_hash_cap enlarges the cell by this factor until the cells fit
-PAIR_CAP_MIN = 1024    # csrc/gvd.hip:1086     cap_first = max(1024, 2 * no); :1166 cap_next = max(1024, P + P / 4)
-PAIR_MIN, PAIR_MAX = 1e-6, 0.5   # csrc/gvd.hip:154  the pairs: 1e-6 < d <= 0.5
+CELLS_PER_ITEM = 2.0   # csrc/dev_prims.h      make_hash_n: at most max(HASH_MIN_CELLS, cells_per_item * n) cells
+HASH_MIN_CELLS = 4096  # csrc/greedy.hip       make_hash_n
+HASH_GROW = 1.25       # csrc/greedy.hip       make_hash_cap enlarges the cell by this factor until the cells fit
+PAIR_CAP_MIN = 1024    # csrc/gvd.hip          kPairCapMin (run_gvd_stage): cap_first = max(1024, 2 * no); cap_next = max(1024, P + P / 4)
+PAIR_MIN, PAIR_MAX = 1e-6, 0.5   # csrc/gvd.hip  kPairMin, kPairMax (pairs_of): the pairs: 1e-6 < d <= 0.5
 
 
 # ---------------------------------------------------------------- grids
@@ -401,7 +401,7 @@ def earlier_conflicts_ends(og):
 
 
 def pair_count(og):
-    """P of run_gvd_stage: pairs i < j of the boundary points with 1e-6 < d <= 0.5 (csrc/gvd.hip:134-166)."""
+    """P of run_gvd_stage: pairs i < j of the boundary points with 1e-6 < d <= 0.5 (csrc/gvd.hip, pairs_of)."""
     from scipy.spatial import cKDTree
     b = og["boundary_raw"]
     if len(b) < 2:
@@ -436,7 +436,7 @@ def rerun_pattern(results):
 
 
 def label_jobs(rows_info):
-    """run_gvd_stage's jobs (csrc/gvd.hip:1093-1103): (ex, ey, ox, oy, deg) per (row, label), 4 per row."""
+    """run_gvd_stage's jobs (csrc/gvd.hip, label_jobs): (ex, ey, ox, oy, deg) per (row, label), 4 per row."""
     r = np.asarray(rows_info, np.float64).reshape(-1, 4)
     jobs = []
     for sx, sy, ex, ey in r:
@@ -447,7 +447,7 @@ def label_jobs(rows_info):
 
 
 def label_candidates(job, nodes, diag2):
-    """k_label_points' test (csrc/gvd.hip:389-403) on every node: (valid mask, distances)."""
+    """k_label_points' test (csrc/gvd.hip, the `test` lambda) on every node: (valid mask, distances)."""
     ex, ey, ox, oy, deg = job
     mdx, mdy = ox - ex, oy - ey
     ml = np.sqrt(mdx * mdx + mdy * mdy)
@@ -475,7 +475,7 @@ def label_regime(rows_info, gr, og):
     x0, x1, y0, y1 = bounds(gr)
     diag2 = np.sqrt((x1 - x0) ** 2 + (y1 - y0) ** 2) * 2.0
     cell = node_index_geometry(gr, og)[0]
-    two_cells = 2.0 * cell * (1.0 - 1e-9)    # csrc/gvd.hip:384 (cell = 1 / cn.h.inv)
+    two_cells = 2.0 * cell * (1.0 - 1e-9)    # csrc/gvd.hip, k_label_points (cell = 1 / cn.h.inv)
     jobs = label_jobs(rows_info)
     valid = og["row_label_valid"].reshape(-1)
     pts = og["row_label_pts"].reshape(-1, 2)

@@ -55,26 +55,26 @@ def oracle_of(name):
     (r"constexpr int kNodeMatch = (\d+);", "gvd.hip", GS.NODE_MATCH),
     (r"constexpr int kNearThreads = (\d+), kNearK = \d+;", "path.hip", GS.NEAR_THREADS),
     (r"constexpr int kNearThreads = \d+, kNearK = (\d+);", "path.hip", GS.NEAR_K),
-    (r"greedy_dedup_async\(G\.dedup, d_raw, nullptr, n, kConflictLessEq, ([\d.]+), hm,", "gvd.hip", GS.MERGE_R),
-    (r"hm = make_hash_n\(g\.minx - ([\d.]+), g\.maxx \+ 60\.0, g\.miny - 60\.0, g\.maxy \+ 60\.0, 0\.5, n\);", "gvd.hip",
-     GS.MERGE_RANGE),
-    (r"h5 = make_hash_n\(g\.minx - 10\.0, g\.maxx \+ 10\.0, g\.miny - 10\.0, g\.maxy \+ 10\.0, ([\d.]+), no\);", "gvd.hip",
-     GS.BP_CELL),
-    (r"h5 = make_hash_n\(g\.minx - ([\d.]+), g\.maxx \+ 10\.0,", "gvd.hip", GS.BP_RANGE),
-    (r"const double thr5 = ([\d.]+) \* 0\.05;", "gvd.hip", GS.BP_THR_SQ ** 0.5),
-    (r"hl = make_hash_n\(g\.minx - 10\.0, g\.maxx \+ 10\.0, g\.miny - 10\.0, g\.maxy \+ 10\.0, ([\d.]+), no\);", "gvd.hip",
-     GS.NODE_CELL),
-    (r"hl = make_hash_n\(g\.minx - ([\d.]+), g\.maxx \+ 10\.0,", "gvd.hip", GS.NODE_RANGE),
-    (r"hq = make_hash_n\(g\.minx - 1\.0, g\.maxx \+ 1\.0, g\.miny - 1\.0, g\.maxy \+ 1\.0, ([\d.]+), nj\);", "gvd.hip",
-     GS.LABEL_CELL),
-    (r"hq = make_hash_n\(g\.minx - ([\d.]+), g\.maxx \+ 1\.0,", "gvd.hip", GS.LABEL_RANGE),
+    # the stage's named constants, at their definitions at the top of gvd.hip
+    (r"constexpr double kMergeRadius = ([\d.]+);", "gvd.hip", GS.MERGE_R),
+    (r"constexpr double kMergeRange = ([\d.]+);", "gvd.hip", GS.MERGE_RANGE),
+    (r"constexpr double kBpCell = ([\d.]+);", "gvd.hip", GS.BP_CELL),
+    (r"constexpr double kBpRange = ([\d.]+);", "gvd.hip", GS.BP_RANGE),
+    (r"constexpr double kBpThr = ([\d.]+);", "gvd.hip", GS.BP_THR_SQ ** 0.5),
+    (r"constexpr double kNodeCell = ([\d.]+);", "gvd.hip", GS.NODE_CELL),
+    (r"constexpr double kNodeRange = ([\d.]+);", "gvd.hip", GS.NODE_RANGE),
+    (r"constexpr double kLabelCell = ([\d.]+);", "gvd.hip", GS.LABEL_CELL),
+    (r"constexpr double kLabelRange = ([\d.]+);", "gvd.hip", GS.LABEL_RANGE),
     (r"long long n, double cells_per_item = ([\d.]+)\);", "dev_prims.h", GS.CELLS_PER_ITEM),
     (r"std::max\(([\d.]+), cells_per_item \* \(double\)std::max\(n, 1LL\)\)", "greedy.hip", GS.HASH_MIN_CELLS),
     (r"c \*= ([\d.]+);", "greedy.hip", GS.HASH_GROW),
-    (r"G\.pairs_cap > 0 \? G\.pairs_cap : std::max\((\d+), 2 \* no\);", "gvd.hip", GS.PAIR_CAP_MIN),
-    (r"G\.pairs_cap = std::max\((\d+), P_ \+ P_ / 4\);", "gvd.hip", GS.PAIR_CAP_MIN),
-    (r"if \(d <= ([\d.]+) && d > 1e-6\) \{", "gvd.hip", GS.PAIR_MAX),
-    (r"if \(d <= 0\.5 && d > ([\de.-]+)\) \{", "gvd.hip", GS.PAIR_MIN),
+    # the pair capacity's floor, and that both the first capacity and the one a frame leaves take it
+    (r"constexpr int kPairCapMin = (\d+);(?s:.*)\? G\.pairs_cap : std::max\(kPairCapMin, 2 \* F\.no\);", "gvd.hip",
+     GS.PAIR_CAP_MIN),
+    (r"constexpr int kPairCapMin = (\d+);(?s:.*)G\.pairs_cap = std::max\(kPairCapMin, z\.P \+ z\.P / 4\);", "gvd.hip",
+     GS.PAIR_CAP_MIN),
+    (r"constexpr double kPairMin = [\de.-]+, kPairMax = ([\d.]+);", "gvd.hip", GS.PAIR_MAX),
+    (r"constexpr double kPairMin = ([\de.-]+), kPairMax = [\d.]+;", "gvd.hip", GS.PAIR_MIN),
     (r"if \(pass == 0 && !\(z <= ([\d.]+) \* \(1\.0 \+ 1e-12\)\)\) return;", "gvd.hip", 25.0),
     (r"const double two_cells = ([\d.]+) / cn\.h\.inv \* \(1\.0 - 1e-9\);", "gvd.hip", 2.0),
 ])
@@ -87,8 +87,8 @@ def test_predictor_constants_match_the_library(text, path, value):
 def test_rerun_rule_matches_the_library():
     """The rerun rule the pattern predictor restates: rerun iff P > cap, once."""
     src = (CSRC / "gvd.hip").read_text()
-    assert re.search(r"if \(P_ <= cap\) \{", src) and re.search(r"if \(attempt\) throw", src)
-    assert re.search(r"const int no = 2 \* ne;", src)
+    assert re.search(r"if \(z\.P <= cap\) break;", src) and re.search(r"if \(attempt\) throw", src)
+    assert re.search(r"F\.no = 2 \* F\.ne;", src)
 
 
 @pytest.mark.parametrize("name", GS.SCENES)
