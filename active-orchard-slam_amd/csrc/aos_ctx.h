@@ -1,5 +1,8 @@
 // Per-handle state of libaos_gpu.so. Not part of the ABI. Every buffer member frees itself with the handle;
 // release() (seedgen.hip) stops the threads and destroys the streams and events first.
+// Methods by file: seedgen.hip the frame (release, run_seedgen*, the thinning driver, the grid copies, finish_frame,
+// debug_grid); cloud_upload.hip the cloud upload, the prefetch and the streaming map's ingest; ror_stage.hip the
+// ROR stage; tiled.hip the tiled frame; gvd_handle.hip the GVD; path.hip the planner.
 #pragma once
 #include <array>
 #include <condition_variable>
@@ -16,12 +19,40 @@
 #include "grid_host.h"
 #include "gvd.h"
 #include "host_pool.h"
+#include "ror.h"
+
+// Indices of aos_ctx::ev, recorded on the handle's stream in frame order unless said otherwise. AsyncGvd::ev uses
+// the kEvGvd* four only (run_gvd_stage). The numbers are the ones the code grew up with.
+enum FrameEvent : int {
+    kEvFrameBegin = 0,       // before the frame's first launch
+    kEvRorEnd = 1,           // a1-a4 done: the raster bits are complete
+    kEvGridEnd = 2,          // a5-a6: inflated (a tiled frame: after the raster halo exchange)
+    kEvThinEnd = 3,          // a7: the skeleton is picked
+    kEvClusterEnd = 4,       // a8-a10 (run_cluster_seed_stage records it; a non-root tiled rank: its frame's end)
+    kEvSeedsEnd = 5,         // a11-a15: the frame's end
+    kEvGridsGathered = 6,    // a tiled frame: the grids are on the root, the distributed cluster stage begins ...
+    kEvGvdBegin = 6,         // ... and, later, on the same handle: run_gvd_stage begins (never both in flight)
+    kEvGvdMerged = 7,        // the seeds are merged
+    kEvGvdEdges = 8,         // the Voronoi edges are on the device: the graph kernels begin
+    kEvGvdEnd = 9,           // the graph's outputs are gathered
+    kEvRorTilesBegin = 10,   // the ROR scatter is done, the tile pass begins
+    kEvRorTilesEnd = 11,     // the tile pass (k_rt_ror, a streaming map's merge and sum included) is done
+    kEvRorCountBegin = 12,   // the count pass (count + column scan) begins
+    kEvRorCountEnd = 13,
+    kEvRorScatterBegin = 14, // after the sizing read-back, if the frame needed one
+    kEvUploadGate = 15,      // the uploader's streams wait for it: the work queued before a host cloud is overwritten
+    kEvStageBegin = 16,      // 16, 17: AOS_TRACE splits of the cluster stage (run_cluster_seed_stage takes the pair)
+    kEvStageGpuEnd = 17,
+    kEvCount
+};
 
 struct aos_ctx {
     aos_params P{};
     int device = 0;
     hipStream_t stream = nullptr;
-    std::array<hipEvent_t, 18> ev{};   // (16, 17: AOS_TRACE splits of the cluster stage)
+    std::array<hipEvent_t, kEvCount> ev{};
+    // elapsed ms between two of them (both recorded and reached)
+    float ms_ev(FrameEvent a, FrameEvent b) const { float t = 0; (void)hipEventElapsedTime(&t, ev[a], ev[b]); return t; }
     aos::Poly poly;
 
     // ---- last cloud (reprocess reuses it: seed_gen:244, 283-285)
@@ -42,35 +73,12 @@ struct aos_ctx {
     uint64_t map_total = 0;
     aos::DevBuf map_count;
     aos::PinnedBuf h_map_count;
-    // ---- tile store of the streaming map (incremental ROR, seedgen.hip ror_stage): the map's binned
-    // points partitioned by ROR tile (own + halo copies, ping-pong), tile starts, kept candidates per
-    // tile; valid while the geometry, density and raster bits are the ones it was built with
-    struct MapStore {
-        bool valid = false;
-        aos::RorLaunch L{};          // geometry it was built with (pointers / counts cleared)
-        aos::DevBuf st[2], ts[2], kept, scan_st, scan_H, scan_ts;
-        int cur = 0, dense = 1;
-        uint64_t n_points = 0;       // map points it covers
-        double n_binned = 0;         // binned (own) points it holds
-        size_t n_staged = 0;         // staged copies it holds
-        // what this frame's ROR stage built, committed by ror_collect after the read-back
-        struct Pending {
-            bool on = false, incremental = false;
-            aos::RorLaunch L{};
-            int dense = 1;
-            uint64_t n_points = 0;
-            int cur = 0;
-        } pend;
-    } ms;
-    uint64_t map_scan_begin = 0;     // map points before the last aos_map_append
-
     // ---- device buffers
-    aos::DevBuf cloud_copy, bin_count, bin_start, sorted, ror_scratch, ror_bigbins, counters;
+    aos::DevBuf cloud_copy;
     aos::DevBuf raster_bits, infl_bits, open_bits, thin_a, thin_b, thin_act, occ_bytes, skel_bytes, flags;
     aos::DevBuf thin_out;   // the converged skeleton bits, picked on the device (launch_thin_pick)
-    aos::LookBackScratch ror_lb;           // look-back words of the ROR column scan (k_rt_colscan)
     aos::DevBuf full_infl, full_skel;      // tiled frames: the whole map, assembled on the root rank
-    aos::PinnedBuf h_small, h_stats;
+    aos::PinnedBuf h_small;
     // Host -> device upload of a large pageable buffer (a PointCloud2 message): kUpThreads host
     // threads copy 2 MB chunks into rings of pinned slots, each DMA'd on the thread's stream (tools/upload_ab.py:
     // 4-8 threads and 1-8 MB chunks all upload C2's 120 MB in 3-4 ms on the box, the H2D DMA's ~40 GB/s).
@@ -148,9 +156,18 @@ struct aos_ctx {
                           int *d_flags, int *d_act, int nflags, int &batch_n, int cap_launches,
                           const std::function<void(int)> &launch_next, const std::function<void()> &after_open);
     uint64_t n_ror_kept = 0, n_clipped = 0;
-    double ror_est_binned = 0;             // binned points of the last frame (sizes the ROR tiles)
-    double ror_staged_max = 0;             // largest staged (own + halo) count seen (sizes the scatter)
-    bool ror_big_seen = false;             // a frame had a ROR tile beyond the LDS capacity (ror.hip big_ok)
+
+    // ---- ROR stage, a1-a4 (ror.h; ror_stage.hip: these methods)
+    aos::RorStage ror;
+    // a1-a4 into the bit window rbits for the cells o owns; allow_guess: the frame may be redone (ror_collect)
+    void ror_stage(const aos::FrameGeom &g, const aos::RorOwn &o, uint64_t *rbits, bool allow_guess);
+    // after the frame's sync: true if the attempt failed (an overflow, a big tile, a stuck look-back)
+    bool ror_collect(bool throw_stuck = true);
+    void ror_stats_to_host(const int *d_staged_total, const aos::RorStatus *d_st);   // queues the stats' read-back
+    void ror_stage_append(aos::RorLaunch L, uint64_t *rbits);   // streaming map: one scan on the tile store
+    aos::LookBack ror_lookback(const aos::RorLaunch &L, int G, aos::RorStatus *d_st);
+    void ror_stage_unchanged();   // streaming map: no new points since the committed store
+    void ror_times(aos_seedgen_out &out);   // n_binned and the three ms_ror_* of a collected frame
 
     // ---- cluster / row / seed stage (cluster_seed.hip); tiled frames: distributed a8-a10 (cluster_dist.hip)
     aos::ClusterSeedState cs;
@@ -187,7 +204,7 @@ struct aos_ctx {
         bool busy = false, quit = false, pub = false, done = false, prefix = false;
         std::exception_ptr err;
         hipStream_t stream = nullptr;
-        std::array<hipEvent_t, 16> ev{};
+        std::array<hipEvent_t, kEvGvdEnd + 1> ev{};   // (FrameEvent: the kEvGvd* four)
         hipEvent_t ready = nullptr;               // the snapshot copy on the seed-gen stream
         std::vector<double> seeds, rows;          // snapshot of h_voronoi / h_rows_info
         aos_grid_info info{};
@@ -216,23 +233,12 @@ struct aos_ctx {
     // ---- path planning (path.hip)
     void *path_state = nullptr;   // aos::PathState
 
-    // Cells a frame rasterises / counts: [rx0, rx1) x [ry0, ry1) (clamped cell), stored into the
-    // Wr x Hr bit window at cell (wx0, wy0), wx0 a multiple of 64; limit_box: bin only points in box
-    // (a tile's shard).
-    struct RorOwn { int rx0, ry0, rx1, ry1, wx0, wy0, Wr, Hr; bool limit_box; float box[4]; };
-
+    // ---- cloud upload, prefetch and streaming map ingest (cloud_upload.hip)
     void set_cloud(const aos_cloud_view &v);
     void map_append(const aos_cloud_view &scan);
     void map_append_box(const aos_cloud_view &scan, const float box[4]);   // tiled streaming map
     void map_grow(uint64_t n);
-    void ror_stage(const aos::FrameGeom &g, const RorOwn &o, uint64_t *rbits, bool allow_guess);
-    bool ror_collect(bool throw_stuck = true);
-    void ror_stats_to_host(const int *d_staged_total, const unsigned long long *d_own);   // after the stream synchronised: true if the ROR scatter overflowed
-    void ror_stage_append(aos::RorLaunch L, uint64_t *rbits);   // streaming map: one scan on the tile store
-    aos::LookBack ror_lookback(const aos::RorLaunch &L, int G, unsigned long long *d_own);
-    void ror_stage_unchanged();   // streaming map: no new points since the committed store
-    uint64_t ror_skipped = 0;     // frames that skipped the ROR stage that way
-    uint64_t ror_read = 0;        // points this frame's partition passes read (aos_seedgen_out::n_ror_read)
+    // ---- the frame (seedgen.hip; tiled.hip: run_tiled*, tile_halo_exchange)
     void finish_frame(const aos::FrameGeom &g, bool want_host, const uint64_t *clipped_total, aos_seedgen_out &out,
                       const aos::PreClusters *pre = nullptr);
     void run_seedgen(bool want_host, aos_seedgen_out &out);

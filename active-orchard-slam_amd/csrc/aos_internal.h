@@ -138,56 +138,7 @@ struct FrameGeom {
     int R;                             // inflation cells
 };
 
-// ------------------------------------------------------------------ kernels (launchers)
-constexpr int kRorCounters = 256;   // spread n_clipped counter slots (k_rt_ror)
-struct RorLaunch {
-    const uint8_t *cloud; uint64_t n; uint32_t step, ox, oy, oz; int is_dense;
-    float bminx, bminy, bminz, bmaxx, bmaxy, bmaxz, inv_cs; int nbx, nby;
-    float cminx, cmaxx, cminy, cmaxy, cminz, cmaxz;
-    double r2; float r2f, r2df; int need;   // r2df: largest float f with (double)f <= r2
-    float r2cmp;   // the keep test as one compare, d2 <= r2cmp (rt_configure: r2df, or the float below r2f)
-    double origin_x, origin_y; float res; int W, H;
-    // Ownership (tiled frames, tiled.hip): a kept candidate is counted iff its cell, clamped to the
-    // grid, lies in [rx0, rx1) x [ry0, ry1); it is rastered (if inside the grid) into the byte window
-    // whose cell (wx0, wy0) is element 0, row pitch Wr. Single-GPU frames own the whole grid.
-    int rx0, ry0, rx1, ry1, wx0, wy0, Wr;
-    // tile walk (ror.hip): TB x TB bins per tile, ntx x nty tiles; the raster window as bits (Hr rows
-    // of WWr words, wx0 a multiple of 64); a tile's LDS raster window (win_rows x win_w words, 0: none)
-    int TB, TBs, ntx, nty, ntiles, Hr, WWr, win_rows, win_w;   // TB = 1 << TBs
-    int staged_cap; int *overflow;   // staged array capacity; | 1 when the scatter exceeds it, | 2 when a tile
-                                     // beyond the LDS capacity was found with big_ok = 0 (the frame is redone)
-    int big_ok;                      // launch the big-tile kernels (ror.hip); 0 skips their five launches
-};
-constexpr int kRtMaxTiles = 36000;   // tiles per frame (LDS histogram of the partition passes: 144 KB)
-void rt_configure(RorLaunch &L, int Hr, int WWr, double est_binned, int force_tb = 0);
-int rt_part_blocks(const RorLaunch &L);   // G: workgroups (= cloud chunks) of the partition passes
-// H: rt_h_ints ints, G x ntiles (row per workgroup) + G per-workgroup binned counts. The count pass (two
-// launches: count, k_rt_colscan) leaves per-tile prefixes over the workgroups in H, the tile starts in ts
-// (ntiles + 1 entries, ts[ntiles] = staged total) and the binned count in *n_own; lb: a look-back of
-// rt_colscan_words words whose err word gets bit 4 on a stuck wait.
-struct LookBack;
-size_t rt_h_ints(const RorLaunch &L, int G);
-int rt_colscan_words(const RorLaunch &L, int G);
-// clr: buffers the count launch zeroes before the stage's later kernels write them (no fill launches)
-struct RtClear { uint64_t *w = nullptr; size_t nw = 0; unsigned long long *c = nullptr; int nc = 0; int *k = nullptr; int nk = 0; };
-void launch_rt_count(const RorLaunch &L, int *H, int G, int *ts, unsigned long long *n_own, const LookBack &lb,
-                     hipStream_t s, const RtClear &clr = RtClear{});
-void launch_rt_scatter(const RorLaunch &L, int *H, const int *tstart, int G, float4 *staged, hipStream_t s);
-// kept_tile (nullable): per-tile kept counts; dirty (nullable): a tile is counted iff dirty[t+1] > dirty[t]
-// scratch: staged-sized; bigbins: rt_bigbins_ints(L) ints (tiles beyond the LDS capacity are sorted there)
-size_t rt_bigbins_ints(const RorLaunch &L);
-int rt_lds_tile_cap();   // records a tile may hold for k_rt_ror<false> (LDS); larger tiles take the big-tile kernels
-// kept_tile != nullptr (a streaming map's store): kept candidates are marked (w = 2) in staged, which
-// is rewritten bin-sorted per tile
-void launch_rt_ror(const RorLaunch &L, const int *tstart, float4 *staged, float4 *scratch, int *bigbins,
-                   uint64_t *rbits, unsigned long long *counters, int *kept_tile, const int *dirty, hipStream_t s);
-// streaming map: merge the map's tile store with a scan's partition; n_clipped from per-tile counts
-// (cap: new_st capacity in records; a merge that would exceed it writes nothing past it and sets *overflow)
-void launch_rt_merge(const float4 *old_st, const int *old_ts, const float4 *scan_st, const int *scan_ts, float4 *new_st,
-                     int *new_ts, int ntiles, int cap, int *overflow, hipStream_t s);
-void launch_rt_sum_kept(const int *kept_tile, int ntiles, unsigned long long *counters, hipStream_t s);
-// reads n staged records (brings their lines into the Infinity Cache before the scatter writes them)
-void launch_rt_touch(const float4 *p, size_t n, hipStream_t s);
+// ------------------------------------------------------------------ kernels (launchers; the ROR stage's: ror.h)
 // PointCloud2 records (any float32 x/y/z offsets) -> float4 (x, y, z, 0)
 void launch_pack_xyz(const uint8_t *cloud, uint64_t n, uint32_t step, uint32_t ox, uint32_t oy, uint32_t oz, float4 *out,
                      hipStream_t s);
@@ -224,8 +175,11 @@ void launch_thin_pick(const int *flags, int launched, const uint64_t *b0, const 
                       hipStream_t s, int *h_flags = nullptr, int nh = 0);
 
 // ------------------------------------------------------------------ frame helpers (seedgen.hip)
+// getActiveBounds (seed_gen:874-890): the polygon's bounding box +- 2.5 m, as the floats the reference keeps
+// (the grid's extent, frame_geom; the corners of markPolygonBoundaryAsOccupied's rectangle, finish_frame)
+struct ActiveBounds { float minx, maxx, miny, maxy; };
+ActiveBounds active_bounds(const Poly &poly);
 FrameGeom frame_geom(const Poly &poly, const aos_params &P);
-float ror_margin(const aos_params &P);
 Poly default_polygon();
 int thin_iterations(const int *flags, int iters_run);
 

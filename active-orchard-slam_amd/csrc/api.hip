@@ -202,7 +202,7 @@ int aos_map_reset(aos_ctx *c, uint64_t reserve_points) {
     c->map_n = 0;
     c->map_total = 0;
     c->map_boxed = false;
-    c->ms.valid = false;
+    c->ror.ms.valid = false;
     c->map_dense = 1;
     if (reserve_points) c->map_buf.ensure(sizeof(float4) * reserve_points);
     return AOS_OK;

@@ -1,5 +1,5 @@
 // Host gather of PointCloud2 records into packed float x, y, z (12 B per point): the uploader's inner loop
-// (seedgen.hip upload_pack). Plain C++ (no device code); tests/sanitize/san_split.cpp checks it.
+// (cloud_upload.hip upload_pack). Plain C++ (no device code); tests/sanitize/san_split.cpp checks it.
 #pragma once
 #include <cstddef>
 #include <cstdint>

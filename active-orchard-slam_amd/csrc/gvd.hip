@@ -20,6 +20,7 @@
 #include <stdexcept>
 #include <vector>
 
+#include "aos_ctx.h"
 #include "dev_prims_device.h"
 #include "gvd.h"
 
@@ -1071,7 +1072,7 @@ bool run_gvd_stage(GvdState &G, const aos_params &P, const GvdStageIn &in, hipSt
     G.merged_xy.clear(); G.row_label_xy.clear(); G.row_label_valid.clear();
     if (G.cells) { G.cells->cell_off.assign(1, 0); G.cells->ms = 0; }
     int *h_sc = static_cast<int *>(G.h_misc.ensure(4096));
-    AOS_HIP(hipEventRecord(ev[6], s));
+    AOS_HIP(hipEventRecord(ev[kEvGvdBegin], s));
     if (in.n_seeds <= 0) return false;  // processGraph: voronoi_seeds_.empty() -> return (gvd:257)
 
     GraphFrame F{};
@@ -1080,7 +1081,7 @@ bool run_gvd_stage(GvdState &G, const aos_params &P, const GvdStageIn &in, hipSt
 
     std::vector<double> merged;
     G.n_merged = merge_seeds(G, S, F.g, in, h_sc, s, tr, merged);
-    AOS_HIP(hipEventRecord(ev[7], s));
+    AOS_HIP(hipEventRecord(ev[kEvGvdMerged], s));
     G.merged_xy = merged;
     if (P.gvd_markers) markers_start(G, P.subdiv_rect_mode);
     if (in.on_host_phase) in.on_host_phase(in.hook_arg);
@@ -1091,7 +1092,7 @@ bool run_gvd_stage(GvdState &G, const aos_params &P, const GvdStageIn &in, hipSt
     auto t1 = std::chrono::steady_clock::now();
     G.ms_delaunay = std::chrono::duration<float, std::milli>(t1 - t0).count();
     G.n_vor_edges = F.ne;
-    AOS_HIP(hipEventRecord(ev[8], s));
+    AOS_HIP(hipEventRecord(ev[kEvGvdEdges], s));
     if (F.ne == 0) {   // no boundary points: an empty graph is still published
         G.have_markers = P.gvd_markers != 0;
         G.graph_ok = true;
@@ -1118,14 +1119,14 @@ bool run_gvd_stage(GvdState &G, const aos_params &P, const GvdStageIn &in, hipSt
     G.n_bpts = z.M;
     tr.mark("graph");
 
-    fill_evals(G, F, z, gather_outputs(G, S, F, z, s, ev[9], tr));
+    fill_evals(G, F, z, gather_outputs(G, S, F, z, s, ev[kEvGvdEnd], tr));
     G.have_markers = P.gvd_markers != 0;
     G.graph_ok = true;
     float a = 0, b = 0;
-    (void)hipEventElapsedTime(&a, ev[6], ev[7]);
-    (void)hipEventElapsedTime(&b, ev[8], ev[9]);
+    (void)hipEventElapsedTime(&a, ev[kEvGvdBegin], ev[kEvGvdMerged]);
+    (void)hipEventElapsedTime(&b, ev[kEvGvdEdges], ev[kEvGvdEnd]);
     G.ms_merge = a; G.ms_graph = b;
-    (void)hipEventElapsedTime(&G.ms_total, ev[6], ev[9]);
+    (void)hipEventElapsedTime(&G.ms_total, ev[kEvGvdBegin], ev[kEvGvdEnd]);
     return true;
 }
 

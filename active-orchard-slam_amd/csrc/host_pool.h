@@ -1,5 +1,5 @@
 // A fixed set of host worker threads that run one indexed job at a time (the uploader's gather,
-// seedgen.hip upload_pack). Spawning the gather threads per frame started the last of them ~0.15 ms after
+// cloud_upload.hip upload_pack). Spawning the gather threads per frame started the last of them ~0.15 ms after
 // the first; parked workers are woken together.
 #pragma once
 #include <sched.h>

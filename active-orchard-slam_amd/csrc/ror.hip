@@ -33,8 +33,8 @@
 #include <stdexcept>
 #include <type_traits>
 
-#include "aos_internal.h"
 #include "dev_prims_device.h"
+#include "ror.h"
 
 namespace aos {
 
@@ -128,30 +128,11 @@ __device__ __forceinline__ bool rt_in(const RorLaunch &L, float4 p, float4 q) {
 // the totals gives the tile starts, and the scatter pass walks the same chunk again with LDS
 // cursors starting at tile start + prefix. No global atomics; a tile's run from workgroup w sits
 // right after workgroup w - 1's.
-// block sizes: the count pass runs best at 256 threads, the scatter pass at 512 (measured,
-// tools/rorbench); both walk the same per-workgroup chunks (a multiple of kRtChunkQ points)
-#ifndef AOS_RT_CPER
-#define AOS_RT_CPER 8
-#endif
-#ifndef AOS_RT_SPER
-#define AOS_RT_SPER 4
-#endif
-#ifndef AOS_RT_CTB
-#define AOS_RT_CTB 256
-#endif
-#ifndef AOS_RT_G
-#define AOS_RT_G 512
-#endif
-#ifndef AOS_RT_STB   // scatter pass block size
-#define AOS_RT_STB 512
-#endif
-#ifndef AOS_RT_COLROWS   // rows of H per k_rt_colscan block
-#define AOS_RT_COLROWS 32
-#endif
-#ifndef AOS_RT_NT   // nontemporal cloud loads: bit 0 count pass, bit 1 scatter pass
-#define AOS_RT_NT 0
-#endif
-constexpr int kRtCountPer = AOS_RT_CPER, kRtScatterPer = AOS_RT_SPER, kRtCountTB = AOS_RT_CTB, kRtScatterTB = AOS_RT_STB;
+// block sizes: the count pass runs best at 256 threads (8 points per thread in flight), the scatter pass at 512
+// (4 per thread), over at most kRtPartBlocks workgroups (measured, tools/rorbench; these and kColRows were
+// build-time macros while they were tuned); both passes walk the same per-workgroup chunks (a
+// multiple of kRtChunkQ points)
+constexpr int kRtCountPer = 8, kRtScatterPer = 4, kRtCountTB = 256, kRtScatterTB = 512, kRtPartBlocks = 512;
 constexpr int kRtChunkQ = 4096;   // chunk granularity (points): a multiple of both passes' sub-chunks
 
 // tiles whose bins a point's 3 x 3 bins touch: [tx0, tx1] x [ty0, ty1], own tile (bx / TB, by / TB)
@@ -193,11 +174,7 @@ __global__ __launch_bounds__(kRtTB) void k_rt_part(RorLaunch L, int *H, const in
     using Rec = typename std::conditional<LAY == 1, float4, float3>::type;
     auto ld = [&](unsigned i, Rec &o) {
         const uint8_t *rec = cbase + i * (unsigned)(LAY == 1 ? 16 : LAY == 2 ? 12 : L.step);
-        if (LAY != 0 && (AOS_RT_NT & (SCATTER ? 2 : 1))) {
-            typedef float vrec __attribute__((ext_vector_type(LAY == 1 ? 4 : 3)));
-            const vrec v = __builtin_nontemporal_load(reinterpret_cast<const vrec *>(rec));
-            o.x = v.x; o.y = v.y; o.z = v.z;
-        } else if (LAY == 0) {
+        if (LAY == 0) {
             o.x = *reinterpret_cast<const float *>(rec + L.ox);
             o.y = *reinterpret_cast<const float *>(rec + L.oy);
             o.z = *reinterpret_cast<const float *>(rec + L.oz);
@@ -250,17 +227,8 @@ __global__ __launch_bounds__(kRtTB) void k_rt_part(RorLaunch L, int *H, const in
                     const int t = ty * L.ntx + tx;
                     const int w = t == otile ? cls : 0;   // a halo copy is never tested there
                     const int pos = atomicAdd(&hist[t], 1);
-                    if (pos < L.staged_cap) {                   // else: overflow, the frame is redone
-                        const float4 v = make_float4(x, y, z, __int_as_float(w));
-                        if (AOS_RT_NT & 4) {
-                            typedef float v4f __attribute__((ext_vector_type(4)));
-                            __builtin_nontemporal_store(v4f{v.x, v.y, v.z, v.w}, reinterpret_cast<v4f *>(staged + pos));
-                        } else {
-                            staged[pos] = v;
-                        }
-                    } else {
-                        *L.overflow = 1;
-                    }
+                    if (pos < L.staged_cap) staged[pos] = make_float4(x, y, z, __int_as_float(w));
+                    else *L.overflow = kRorStagedOverflow;   // the frame is redone
                 }
         }
     };
@@ -298,14 +266,14 @@ __global__ __launch_bounds__(kRtTB) void k_rt_part(RorLaunch L, int *H, const in
 // rows as running prefixes; the last row group's blocks then hold the tile totals and chain the tile-start
 // scan over b. Blocks take ids in launch order, row-group major, so a block only waits for blocks of smaller
 // ids (started before it): no deadlock whatever the dispatch order. Words carry the launch's epoch (no init).
-constexpr int kColRows = AOS_RT_COLROWS, kColTB = 256;
+constexpr int kColRows = 32, kColTB = 256;   // rows of H per k_rt_colscan block; its block size
 struct ColScan {
     int *H;                  // G rows of ntiles counts -> exclusive prefixes over the rows
     int *ts;                 // [ntiles + 1] tile starts
     const unsigned *own;     // [G] binned points per count workgroup
-    unsigned long long *n_own;   // [0] binned points, [2] the largest tile's record count (atomicMax)
+    RorStatus *st;           // binned: the binned points; largest_tile: the largest tile's record count (atomicMax)
     int ntiles, G, ng, ntb;
-    LookBack L;              // part: ng x ntiles column words, then ntb tile-chain words; err bit 4 on a stuck wait
+    LookBack L;              // part: ng x ntiles column words, then ntb tile-chain words; err | kRorStuckLookBack
 };
 __global__ __launch_bounds__(kColTB) void k_rt_colscan(ColScan C) {
     __shared__ int sh_vid, wsum[kColTB / 64], sh_tot, sh_pre;
@@ -314,7 +282,7 @@ __global__ __launch_bounds__(kColTB) void k_rt_colscan(ColScan C) {
     if (tid == 0) {
         const unsigned v = atomicAdd(C.L.ticket, 1u);
         if (v == gridDim.x - 1) __hip_atomic_store(C.L.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (v >= gridDim.x) atomicOr(C.L.err, 4);
+        if (v >= gridDim.x) atomicOr(C.L.err, kRorStuckLookBack);
         sh_vid = (int)(v % gridDim.x);
     }
     __syncthreads();
@@ -343,7 +311,7 @@ __global__ __launch_bounds__(kColTB) void k_rt_colscan(ColScan C) {
                     const unsigned tag = (unsigned)(x >> 32);
                     flag = (tag >> 2) == C.L.epoch ? (tag & 3u) : 0u;
                     if (flag) break;
-                    if (++spins > kSpinCap) { atomicOr(C.L.err, 4); flag = 2; x = 0; break; }
+                    if (++spins > kSpinCap) { atomicOr(C.L.err, kRorStuckLookBack); flag = 2; x = 0; break; }
                     __builtin_amdgcn_s_sleep(1);
                 }
                 run += (int)(unsigned)x;
@@ -367,7 +335,7 @@ __global__ __launch_bounds__(kColTB) void k_rt_colscan(ColScan C) {
         if (tid == 0) {
             unsigned long long tot = 0;
             for (int k = 0; k < kColTB / 64; ++k) tot += sh_own[k];
-            *C.n_own = tot;
+            C.st->binned = tot;
         }
     }
     if (g != C.ng - 1) return;   // (uniform per block)
@@ -376,12 +344,12 @@ __global__ __launch_bounds__(kColTB) void k_rt_colscan(ColScan C) {
     {   // the largest tile (a frame that cannot be redone skips the big-tile kernels when it fits the LDS cap)
         int mx = live ? run : 0;
         mx = wave_reduce(mx, 0, WMax());
-        if ((tid & 63) == 0 && mx > 0) atomicMax(C.n_own + 2, (unsigned long long)mx);
+        if ((tid & 63) == 0 && mx > 0) atomicMax(&C.st->largest_tile, (unsigned long long)mx);
     }
     if (tid < 64) {
         LookBack T = C.L;
         T.part += (size_t)C.ng * C.ntiles;
-        const unsigned pre = lb_exclusive(T, b, (unsigned)sh_tot, 4);
+        const unsigned pre = lb_exclusive(T, b, (unsigned)sh_tot, kRorStuckLookBack);
         if (tid == 0) sh_pre = (int)pre;
     }
     __syncthreads();
@@ -391,15 +359,7 @@ __global__ __launch_bounds__(kColTB) void k_rt_colscan(ColScan C) {
 
 // ---------------------------------------------------------------------------------------------
 // Pass 4: per tile, counting sort by bin in LDS, neighbour counts, raster bitmap.
-#ifndef AOS_RT_THREADS
-#define AOS_RT_THREADS 512
-#endif
-constexpr int kRorThreads = AOS_RT_THREADS, kRorCap = 2048, kRorPer = kRorCap / kRorThreads;
-#ifndef AOS_RT_VARIANT   // timing experiments only (tools/rorbench): 1 = no neighbour scan, 2 = no raster,
-                         // 3 = load + bin histogram only, 4 = load + counting sort only
-#define AOS_RT_VARIANT 0
-#endif
-
+constexpr int kRorThreads = 512, kRorCap = 2048, kRorPer = kRorCap / kRorThreads;
 
 // record i of a neighbour list ending at k1 (a batch of 4 may run past it: those records are not counted).
 // A global list (big tiles) is clamped to stay inside its allocation; a fitting tile's LDS list has 3 records
@@ -453,13 +413,7 @@ __device__ __forceinline__ int rt_wave_scan(const RorLaunch &L, float4 p, Pts pt
     return cnt;
 }
 
-#ifndef AOS_RT_BUDGET_LDS
-#define AOS_RT_BUDGET_LDS 12
-#endif
-#ifndef AOS_RT_BUDGET2
-#define AOS_RT_BUDGET2 96
-#endif
-constexpr int kRtBudgetBig = 64, kRtBudgetLds = AOS_RT_BUDGET_LDS, kRtQCap = 512, kRtBudget2 = AOS_RT_BUDGET2, kRtQ2Cap = 128;
+constexpr int kRtBudgetBig = 64, kRtBudgetLds = 12, kRtQCap = 512, kRtBudget2 = 96, kRtQ2Cap = 128;
 
 // LDS of k_rt_ror: kRorCap staged points (32 KB), the bin offsets of the largest tile (TB = 32 bins
 // + ring: 34^2), the tile's raster window (kRtWinWords 64-bit words: 70 rows x 3 words at 0.1 m cells)
@@ -640,6 +594,8 @@ __global__ __launch_bounds__(kRorThreads) void k_rt_ror(RorLaunch L, const int *
                                                         const int *dirty, BigBufs B) {
     __shared__ float4 pts[BIG ? 1 : kRorCap + 3];   // (+ 3: rt_at's padding)
     const LdsList LP{pts};
+    // (the LDS list goes through these three: with pts[...] written out the compiler schedules k_rt_ror<false>
+    // differently, which would want a measurement of its own)
     auto lp_get = [&](int k) { return pts[k]; };
     auto lp_put = [&](int k, float4 v) { pts[k] = v; };
     auto lp_setw = [&](int k, float w) { pts[k].w = w; };
@@ -667,8 +623,8 @@ __global__ __launch_bounds__(kRorThreads) void k_rt_ror(RorLaunch L, const int *
     if (!BIG && dirty && dirty[t + 1] == dirty[t]) return;
     if (!BIG) {
         if (n > kRorCap && a + n <= L.staged_cap) {   // a big tile: k_rt_ror<true>
-            // (not launched this frame: the frame is redone with the big-tile kernels, seedgen.hip)
-            if (!L.big_ok && tid == 0) atomicOr(L.overflow, 2);
+            // (not launched this frame: the frame is redone with the big-tile kernels, ror_collect)
+            if (!L.big_ok && tid == 0) atomicOr(L.overflow, kRorBigTileSeen);
             return;
         }
         if (n == 0 || a + n > L.staged_cap) {               // (an overflowed scatter: the frame is redone)
@@ -709,7 +665,6 @@ __global__ __launch_bounds__(kRorThreads) void k_rt_ror(RorLaunch L, const int *
             rk[j] = k < n ? atomicAdd(&bstart[lb[j] + 1], 1) : -1;
         }
         __syncthreads();
-        if (AOS_RT_VARIANT == 3) return;   // (timing: load + histogram only)
         // exclusive bin offsets: bstart[b] = points in bins < b. Thread t sums a run of kSeg bins,
         // one block scan over the run totals, then each run is written back.
         constexpr int kSeg = (kRtMaxLocalBins + kRorThreads - 1) / kRorThreads;
@@ -739,7 +694,6 @@ __global__ __launch_bounds__(kRorThreads) void k_rt_ror(RorLaunch L, const int *
         for (int j = 0; j < kRorPer; ++j)
             if (rk[j] >= 0) lp_put(bstart[lb[j]] + rk[j], q[j]);
         __syncthreads();
-        if (AOS_RT_VARIANT == 4) return;   // (timing: load + counting sort only)
     }
     float4 *P = const_cast<float4 *>(scratch) + a;
     unsigned kept_n = 0;
@@ -752,11 +706,16 @@ __global__ __launch_bounds__(kRorThreads) void k_rt_ror(RorLaunch L, const int *
     // decision is monotone as points are added: it stays kept, its cell is already in the raster)
     const bool store = kept_tile != nullptr;
     const double res_d = (double)L.res, inv_res = 1.0 / res_d;
-    auto prev_kept = [&](float4 p) {   // kept in an earlier frame: counted, not re-tested
-        const int gx = rt_cell((double)p.x - L.origin_x, res_d, inv_res);
-        const int gy = rt_cell((double)p.y - L.origin_y, res_d, inv_res);
+    // the cell (gx, gy) of a kept record; true iff that cell, clamped to the grid, is an owned one
+    auto kept_cell = [&](float4 p, int &gx, int &gy) {
+        gx = rt_cell((double)p.x - L.origin_x, res_d, inv_res);
+        gy = rt_cell((double)p.y - L.origin_y, res_d, inv_res);
         const int cx = min(max(gx, 0), L.W - 1), cy = min(max(gy, 0), L.H - 1);
-        if (cx >= L.rx0 && cx < L.rx1 && cy >= L.ry0 && cy < L.ry1) ++kept_n;
+        return cx >= L.rx0 && cx < L.rx1 && cy >= L.ry0 && cy < L.ry1;
+    };
+    auto prev_kept = [&](float4 p) {   // kept in an earlier frame: counted, not re-tested
+        int gx, gy;
+        if (kept_cell(p, gx, gy)) ++kept_n;
     };
     auto on_kept = [&](float4 p, int k) {
         if (store) {   // remembered in the tile store (written back below)
@@ -764,12 +723,10 @@ __global__ __launch_bounds__(kRorThreads) void k_rt_ror(RorLaunch L, const int *
             else lp_setw(k, __int_as_float(2));
         }
         // kept: counted iff its clamped cell is owned, rastered iff inside the grid (seed_gen:606-619)
-        const int gx = rt_cell((double)p.x - L.origin_x, res_d, inv_res);
-        const int gy = rt_cell((double)p.y - L.origin_y, res_d, inv_res);
-        const int cx = min(max(gx, 0), L.W - 1), cy = min(max(gy, 0), L.H - 1);
-        if (cx < L.rx0 || cx >= L.rx1 || cy < L.ry0 || cy >= L.ry1) return;
+        int gx, gy;
+        if (!kept_cell(p, gx, gy)) return;
         ++kept_n;
-        if (AOS_RT_VARIANT == 2 || gx < 0 || gx >= L.W || gy < 0 || gy >= L.H) return;
+        if (gx < 0 || gx >= L.W || gy < 0 || gy >= L.H) return;
         const int bxw = gx - L.wx0, r = gy - L.wy0;
         const int wr = r - (cy0 - L.wy0), ww = (bxw >> 6) - cw0;
         const unsigned long long bit = 1ull << (bxw & 63);
@@ -806,7 +763,7 @@ __global__ __launch_bounds__(kRorThreads) void k_rt_ror(RorLaunch L, const int *
         int lx, ly;
         local_of(p, lx, ly);
         const bool counted = BIG && (w & kWCounted);   // the store's points are counted: the new ones only
-        const int nr = counted ? 9 : 3, cnt0 = AOS_RT_VARIANT == 1 ? L.need : (counted ? w >> kWCntShift : 0);
+        const int nr = counted ? 9 : 3, cnt0 = counted ? w >> kWCntShift : 0;
         int cnt = cnt0, budget = BIG ? kRtBudgetBig : kRtBudgetLds;
         for (int i = 0; i < nr && cnt < L.need && budget >= 0; ++i) {
             int r0, r1;
@@ -872,16 +829,16 @@ __global__ __launch_bounds__(kRorThreads) void k_rt_ror(RorLaunch L, const int *
         } else   // big tiles: one wave each
         for (int i = tid >> 6; i < nq; i += kRorThreads / 64) {
             const int k = q_k[i];
-            const float4 p = BIG ? P[k] : lp_get(k);
+            const float4 p = P[k];
             const int w = __float_as_int(p.w);
             int lx, ly;
             local_of(p, lx, ly);
-            const bool counted = BIG && (w & kWCounted);
+            const bool counted = w & kWCounted;
             int cnt = counted ? w >> kWCntShift : 0;
             for (int r = 0; r < (counted ? 9 : 3) && cnt < L.need; ++r) {
                 int r0, r1;
                 range(counted, lx, ly, r, r0, r1);
-                cnt = BIG ? rt_wave_scan(L, p, P, r0, r1, cnt, lane) : rt_wave_scan(L, p, LP, r0, r1, cnt, lane);
+                cnt = rt_wave_scan(L, p, P, r0, r1, cnt, lane);
             }
             if (lane == 0) decide(p, k, cnt);
         }
@@ -933,7 +890,7 @@ __global__ __launch_bounds__(256) void k_rt_merge(const float4 *old_st, const in
     if (t == ntiles) return;
     const int no = old_ts[t + 1] - o0, ns = scan_ts[t + 1] - s0;
     if ((long long)d0 + no + ns > cap) {   // the host's store size was stale: nothing is written past cap
-        if (threadIdx.x == 0) *overflow = 1;
+        if (threadIdx.x == 0) *overflow = kRorStagedOverflow;
         return;
     }
     // blockIdx.y-th of gridDim.y slices of the tile's runs (a big tile's copy spreads over CUs)
@@ -960,8 +917,9 @@ __global__ __launch_bounds__(1024) void k_rt_sum_kept(const int *kept_tile, int 
 
 // ---------------------------------------------------------------------------------------------
 // est_binned: expected binned points (the previous frame's count, or a guess); it only sizes the
-// tiles (TB = 32 bins, or 16 where tiles would average more than ~1400 points) — results do not
-// depend on it.
+// tiles (TB = 32 bins, or 16 where tiles of 32, with kTileEstSlack on the estimate, would average more than
+// kTilePointsMax points of the kRorCap an LDS tile holds) — results do not depend on it.
+constexpr double kTileEstSlack = 1.15, kTilePointsMax = 1400.0;
 void rt_configure(RorLaunch &L, int Hr, int WWr, double est_binned, int force_tb) {
     auto tiles = [&](int tb) {
         if (tb <= 0 || (tb & (tb - 1))) throw std::runtime_error("ROR tile size must be a power of two");
@@ -974,8 +932,8 @@ void rt_configure(RorLaunch &L, int Hr, int WWr, double est_binned, int force_tb
     if (force_tb && tiles(force_tb) <= kRtMaxTiles) {
         tiles(force_tb);
     } else {
-        const double per32 = est_binned * 1.15 / (double)tiles(32);
-        if (!(per32 > 1400.0 && tiles(16) <= kRtMaxTiles)) tiles(32);
+        const double per32 = est_binned * kTileEstSlack / (double)tiles(32);
+        if (!(per32 > kTilePointsMax && tiles(16) <= kRtMaxTiles)) tiles(32);
     }
     if (tiles(L.TB) > kRtMaxTiles || (L.TB + 2) * (L.TB + 2) > kRtMaxLocalBins)
         throw std::runtime_error("ROR bin grid too large for the tile walk");
@@ -992,7 +950,7 @@ void rt_configure(RorLaunch &L, int Hr, int WWr, double est_binned, int force_tb
 
 int rt_part_blocks(const RorLaunch &L) {
     // one contiguous chunk per workgroup; H has ntiles x G ints
-    long long g = AOS_RT_G;
+    long long g = kRtPartBlocks;
     const long long kRtSub = kRtChunkQ;
     while (g > 64 && (long long)L.ntiles * g > (16ll << 20)) g /= 2;
     return (int)std::max<long long>(1, std::min<long long>(g, ((long long)L.n + kRtSub - 1) / kRtSub));
@@ -1027,8 +985,8 @@ int rt_colscan_words(const RorLaunch &L, int G) {
     return ((G + kColRows - 1) / kColRows) * L.ntiles + (L.ntiles + kColTB - 1) / kColTB;
 }
 
-void launch_rt_count(const RorLaunch &L, int *H, int G, int *ts, unsigned long long *n_own, const LookBack &lb,
-                     hipStream_t s, const RtClear &clr) {
+void launch_rt_count(const RorLaunch &L, int *H, int G, int *ts, RorStatus *st, const LookBack &lb, hipStream_t s,
+                     const RtClear &clr) {
     if (!L.n || !L.ntiles) throw std::logic_error("launch_rt_count: no points or tiles");   // (the callers check)
     unsigned *own = reinterpret_cast<unsigned *>(H + (size_t)L.ntiles * G);
     switch (rt_layout(L)) {
@@ -1036,7 +994,7 @@ void launch_rt_count(const RorLaunch &L, int *H, int G, int *ts, unsigned long l
         case 2: rt_part<false, 2>(L, H, nullptr, G, nullptr, own, s, clr); break;
         default: rt_part<false, 0>(L, H, nullptr, G, nullptr, own, s, clr);
     }
-    ColScan C{H, ts, own, n_own, L.ntiles, G, (G + kColRows - 1) / kColRows, (L.ntiles + kColTB - 1) / kColTB, lb};
+    ColScan C{H, ts, own, st, L.ntiles, G, (G + kColRows - 1) / kColRows, (L.ntiles + kColTB - 1) / kColTB, lb};
     k_rt_colscan<<<C.ng * C.ntb, kColTB, 0, s>>>(C);
     AOS_HIP(hipGetLastError());
 }

@@ -312,7 +312,7 @@ void aos_ctx::tile_halo_exchange(uint64_t *win, const TilePlan &t, FrameComm &fc
 void aos_ctx::run_tiled(const aos_comm &cm, int tiles_x, int tiles_y, int root, bool want_host, aos_seedgen_out &out) {
     FrameComm fc(cm, coll_ev, coll_red);
     const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t skipped0 = ror_skipped;
+    const uint64_t skipped0 = ror.skipped;
     auto record = [&]() {
         tstats = aos_tiled_stats{};
         tstats.ms_frame = (float)ms_since(t0);
@@ -327,7 +327,7 @@ void aos_ctx::run_tiled(const aos_comm &cm, int tiles_x, int tiles_y, int root, 
         tstats.ms_cluster_global = cdist_stats.ms_global;
         tstats.ms_replay = cdist_stats.ms_replay;
         tstats.n_replayed = cdist_stats.n_replayed_here;
-        tstats.ror_skipped = ror_skipped != skipped0 ? 1 : 0;
+        tstats.ror_skipped = ror.skipped != skipped0 ? 1 : 0;
         tstats.is_root = cm.rank == root ? 1 : 0;
     };
     try {
@@ -363,20 +363,20 @@ void aos_ctx::run_tiled_frame(FrameComm &fc, int tiles_x, int tiles_y, int root,
     hipStream_t s = stream;
     const FrameGeom &lg = t.lg;
     const size_t Cwl = (size_t)lg.WW * lg.H;
-    AOS_HIP(hipEventRecord(ev[0], s));
+    AOS_HIP(hipEventRecord(ev[kEvFrameBegin], s));
 
     // ---- a1-a4 for the candidates whose cell is an own cell, rastered into the window
     RorOwn own{64 * t.c0, t.y0, std::min(g.W, 64 * t.c1), t.y1, 64 * t.wc0, t.wy0, lg.W, lg.H, true,
                {t.box[0], t.box[1], t.box[2], t.box[3]}};
     uint64_t *d_rbits = static_cast<uint64_t *>(raster_bits.ensure(Cwl * 8));
     ror_stage(g, own, d_rbits, false);   // sized by a read-back: a rank cannot redo a frame alone
-    AOS_HIP(hipEventRecord(ev[1], s));
+    AOS_HIP(hipEventRecord(ev[kEvRorEnd], s));
 
     // ---- raster halo from the neighbours, a5 inflation on the window
     uint64_t *d_ibits = static_cast<uint64_t *>(infl_bits.ensure(Cwl * 8));
     tile_halo_exchange(d_rbits, t, fc);
     launch_inflate(d_rbits, d_ibits, lg, s);
-    AOS_HIP(hipEventRecord(ev[2], s));
+    AOS_HIP(hipEventRecord(ev[kEvGridEnd], s));
 
     // ---- a7 opening + Zhang-Suen in halo periods
     uint64_t *d_open = static_cast<uint64_t *>(open_bits.ensure(Cwl * 8));
@@ -418,18 +418,19 @@ void aos_ctx::run_tiled_frame(FrameComm &fc, int tiles_x, int tiles_y, int root,
         }
     }
     thin_iters = T;
-    AOS_HIP(hipEventRecord(ev[3], s));
+    AOS_HIP(hipEventRecord(ev[kEvThinEnd], s));
 
     // ---- kept candidates over all tiles: each rank fills its own slot, max = sum of the slots
-    unsigned long long *h_cnt = static_cast<unsigned long long *>(h_stats.ensure(64 + 8 * kRorCounters)) + 8;
-    AOS_HIP(hipMemcpyAsync(h_cnt, counters.p, 8 * kRorCounters, hipMemcpyDeviceToHost, s));
+    RorHostStats *h_ror = ror.stats();
+    unsigned long long *h_cnt = h_ror->kept;
+    AOS_HIP(hipMemcpyAsync(h_cnt, ror.counters.p, sizeof(RorCounters::kept), hipMemcpyDeviceToHost, s));
     AOS_HIP(hipStreamSynchronize(s));
     // (sized by a read-back, so no staging overflow is expected; a streaming store's merge can still
     // overflow a stale size: the bits travel with the counts and every rank fails the frame together)
     if (g_debug_stuck_rank.load(std::memory_order_relaxed) == cm.rank)   // (tests: this rank's column scan "got stuck")
-        reinterpret_cast<unsigned long long *>(static_cast<int *>(h_stats.p) + 4)[1] |= 4;
-    const bool ror_over = ror_collect(false);   // (bit 4, a stuck look-back, travels with the others)
-    const int ror_bits = ror_over ? (int)reinterpret_cast<const unsigned long long *>(static_cast<const int *>(h_stats.p) + 4)[1] : 0;
+        h_ror->st.flags |= kRorStuckLookBack;
+    const bool ror_over = ror_collect(false);   // (kRorStuckLookBack travels with the others)
+    const int ror_bits = ror_over ? (int)h_ror->st.flags : 0;
     uint64_t mine_cnt = 0;
     for (int i = 0; i < kRorCounters; ++i) mine_cnt += h_cnt[i];
     std::vector<int32_t> slots(2 * (size_t)cm.world + 1, 0);
@@ -439,8 +440,9 @@ void aos_ctx::run_tiled_frame(FrameComm &fc, int tiles_x, int tiles_y, int root,
     fc.max_host(slots.data(), (int)slots.size());
     if (slots[2 * cm.world])
         throw std::runtime_error("tiled frame: ROR stage overflow on a rank (bits " + std::to_string(slots[2 * cm.world]) +
-                                 ": 1 staged capacity / store merge, 2 a tile beyond the LDS capacity, 4 a stuck look-back "
-                                 "wait in the ROR column scan)");
+                                 ": " + std::to_string(kRorStagedOverflow) + " staged capacity / store merge, " +
+                                 std::to_string(kRorBigTileSeen) + " a tile beyond the LDS capacity, " +
+                                 std::to_string(kRorStuckLookBack) + " a stuck look-back wait in the ROR column scan)");
     uint64_t total = 0;
     for (int r = 0; r < cm.world; ++r) total += (uint64_t)slots[2 * r] | ((uint64_t)slots[2 * r + 1] << 31);
 
@@ -465,7 +467,7 @@ void aos_ctx::run_tiled_frame(FrameComm &fc, int tiles_x, int tiles_y, int root,
     }
 
     // ---- a8-a10 over the ranks: own-tile labelling, border union-find, shared statistics / replays
-    AOS_HIP(hipEventRecord(ev[6], s));
+    AOS_HIP(hipEventRecord(ev[kEvGridsGathered], s));
     PreClusters pre;
     cluster_dist(cdist, fc, t, g, poly, static_cast<float>(P.cluster_min_length), cur, root, s, pre, cdist_stats);
     if (cm.rank == root) {
@@ -478,14 +480,11 @@ void aos_ctx::run_tiled_frame(FrameComm &fc, int tiles_x, int tiles_y, int root,
     out.thin_iters = T;
     out.n_input = (d_cloud == map_buf.as<uint8_t>() && n_points == map_n) ? map_total : n_points;
     out.n_clipped = total;
-    auto ms = [&](int a, int b) { float v = 0; (void)hipEventElapsedTime(&v, ev[a], ev[b]); return v; };
-    AOS_HIP(hipEventRecord(ev[4], s));
-    AOS_HIP(hipEventSynchronize(ev[4]));
-    out.ms_ror = ms(0, 1); out.ms_grid = ms(1, 2); out.ms_thin = ms(2, 3); out.ms_cluster = ms(6, 4);
-    out.ms_total = ms(0, 4);
-    out.n_binned = static_cast<const int *>(h_stats.p)[0];
-    out.ms_ror_count = out.n_binned ? ms(10, 11) : 0.0f;
-    out.ms_ror_bin = out.n_binned ? ms(12, 13) : 0.0f;
-    out.ms_ror_scatter = out.n_binned ? ms(14, 10) : 0.0f;
-    out.n_ror_read = ror_read;
+    AOS_HIP(hipEventRecord(ev[kEvClusterEnd], s));
+    AOS_HIP(hipEventSynchronize(ev[kEvClusterEnd]));
+    out.ms_ror = ms_ev(kEvFrameBegin, kEvRorEnd); out.ms_grid = ms_ev(kEvRorEnd, kEvGridEnd);
+    out.ms_thin = ms_ev(kEvGridEnd, kEvThinEnd); out.ms_cluster = ms_ev(kEvGridsGathered, kEvClusterEnd);
+    out.ms_total = ms_ev(kEvFrameBegin, kEvClusterEnd);
+    ror_times(out);
+    out.n_ror_read = ror.read;
 }

@@ -82,7 +82,7 @@ def assert_gvd_full_parity(ctx, g: dict, o: dict):
 
 
 def binned_box(poly, ror_radius=0.2, minz=-0.4, maxz=0.5):
-    """seedgen.hip binned_box / ror_stage: frame_geom's float bounds (polygon +- 2.5 m, double -> float)
+    """ror_stage.hip ror_binned_box / ror_stage: frame_geom's float bounds (polygon +- 2.5 m, double -> float)
     minus / plus ror_margin, in float32 as on the host."""
     f = np.float32
     m = f(f(ror_radius * 1.01) + f(1e-4))

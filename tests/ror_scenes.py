@@ -1,5 +1,5 @@
 """Designed clouds for the front of the frame: radius outlier removal, PassThrough, the exclusion discs and the raster
-(csrc/ror.hip, ror_stage / ror_stage_append / ror_collect of csrc/seedgen.hip). Test infrastructure, imported like
+(csrc/ror.hip, ror_stage / ror_stage_append / ror_collect of csrc/ror_stage.hip). Test infrastructure, imported like
 shapes.py.
 
 The observability device: a *probe* is a clip candidate that is alone in its grid cell, so its raster bit (and its
@@ -23,22 +23,22 @@ from shapes import MARGIN, ORIGIN, RES, rect_polygon
 F = np.float32
 
 # ---------------------------------------------------------------- the library's constants the predictors use
-ROR_CAP = 2048            # csrc/ror.hip:397   kRorCap (records of a tile that fits LDS)
-BUDGET1 = 12              # csrc/ror.hip:457   AOS_RT_BUDGET_LDS (first pass, points per candidate)
-BUDGET2 = 96              # csrc/ror.hip:460   AOS_RT_BUDGET2 (second pass)
-Q1_CAP = 512              # csrc/ror.hip:462   kRtQCap
-Q2_CAP = 128              # csrc/ror.hip:462   kRtQ2Cap
-BUDGET_BIG = 64           # csrc/ror.hip:462   kRtBudgetBig
-BIG_CHUNK = 4096          # csrc/ror.hip:493   kBigChunk
-WIN_WORDS = 256           # csrc/ror.hip:467   kRtWinWords
-PART_CHUNK = 4096         # csrc/ror.hip:155   kRtChunkQ
-PART_G = 512              # csrc/ror.hip:143   AOS_RT_G
-COL_ROWS = 32             # csrc/ror.hip:149   AOS_RT_COLROWS
-COL_TB = 256              # csrc/ror.hip:301   kColTB
-MAX_TILES = 36000         # csrc/aos_internal.h:161  kRtMaxTiles
-BIN_CAP = 8192.0          # csrc/seedgen.hip:472     the bin grid's cap
-PART_LDS_DEFAULT = 64 * 1024   # csrc/ror.hip:1014  dynamic LDS beyond it needs hipFuncSetAttribute
-TB16_PER32 = 1400.0       # csrc/ror.hip:978   TB = 16 where tiles of 32 would average more records
+ROR_CAP = 2048            # csrc/ror.hip:362   kRorCap (records of a tile that fits LDS)
+BUDGET1 = 12              # csrc/ror.hip:416   kRtBudgetLds (first pass, points per candidate)
+BUDGET2 = 96              # csrc/ror.hip:416   kRtBudget2 (second pass)
+Q1_CAP = 512              # csrc/ror.hip:416   kRtQCap
+Q2_CAP = 128              # csrc/ror.hip:416   kRtQ2Cap
+BUDGET_BIG = 64           # csrc/ror.hip:416   kRtBudgetBig
+BIG_CHUNK = 4096          # csrc/ror.hip:447   kBigChunk
+WIN_WORDS = 256           # csrc/ror.hip:421   kRtWinWords
+PART_CHUNK = 4096         # csrc/ror.hip:136   kRtChunkQ
+PART_G = 512              # csrc/ror.hip:135   kRtPartBlocks
+COL_ROWS = 32             # csrc/ror.hip:269   kColRows
+COL_TB = 256              # csrc/ror.hip:269   kColTB
+MAX_TILES = 36000         # csrc/ror.h:60      kRtMaxTiles
+BIN_CAP = 8192.0          # csrc/ror_stage.hip:56  kMaxBinsPerAxis, the bin grid's cap
+PART_LDS_DEFAULT = 64 * 1024   # csrc/ror.hip:972   dynamic LDS beyond it needs hipFuncSetAttribute
+TB16_PER32 = 1400.0       # csrc/ror.hip:922   kTilePointsMax: TB = 16 where tiles of 32 would average more records
 
 # Exclusion discs of processPointCloud (reference src/aos_seed_gen_node.cpp:487-499): x, y, radius. Data.
 DISCS = np.array([[0.646417, 3.83918, 1.0], [2.0405, 3.62485, 1.0], [65.3711, 2.09755, 1.0], [66.9094, 2.07515, 1.0],
@@ -186,13 +186,14 @@ class Geom:
 
 
 def ror_margin(r):
-    """csrc/seedgen.hip:421 ror_margin: (float)(r * 1.01) + 1e-4f."""
+    """csrc/ror_stage.hip:16 ror_margin: (float)(r * 1.01) + 1e-4f."""
     return F(F(r * 1.01) + F(1e-4))
 
 
 def geometry(polygon, akw, n_read, est_binned=None, step=16, offs=(0, 4, 8), host=False):
-    """ror_stage's launch geometry (csrc/seedgen.hip:456-499) and rt_configure's (csrc/ror.hip:965-991) for a frame
-    whose partition passes read n_read records; est_binned None = a fresh handle (0.5 n, seedgen.hip:499)."""
+    """ror_stage's launch geometry (launch_geometry and bin_grid, csrc/ror_stage.hip:33-69) and rt_configure's
+    (csrc/ror.hip:923-949) for a frame whose partition passes read n_read records; est_binned None = a fresh handle
+    (0.5 n, ror_stage.hip:147)."""
     g = Geom()
     r, res = akw["ror_radius"], F(akw["grid_resolution"])
     (cminx, cmaxx, cminy, cmaxy), g.W, g.H = frame(polygon, res)
@@ -227,7 +228,7 @@ def geometry(polygon, akw, n_read, est_binned=None, step=16, offs=(0, 4, 8), hos
     cells = int(math.ceil(span)) + 6
     g.win_w = (cells + 63) // 64 + 1
     g.win_rows = cells if cells * g.win_w <= WIN_WORDS else 0
-    gg = PART_G                                           # rt_part_blocks, csrc/ror.hip:993
+    gg = PART_G                                           # rt_part_blocks, csrc/ror.hip:951
     while gg > 64 and g.ntiles * gg > (16 << 20):
         gg //= 2
     g.G = max(1, min(gg, (n_read + PART_CHUNK - 1) // PART_CHUNK))
@@ -235,7 +236,7 @@ def geometry(polygon, akw, n_read, est_binned=None, step=16, offs=(0, 4, 8), hos
     g.row_groups = (g.G + COL_ROWS - 1) // COL_ROWS
     g.tile_blocks = (g.ntiles + COL_TB - 1) // COL_TB
     g.part_lds = 4 * g.ntiles
-    # rt_layout (csrc/ror.hip:1020); a host cloud is packed to float3 by the upload (LAY 2)
+    # rt_layout (csrc/ror.hip:978); a host cloud is packed to float3 by the upload (LAY 2)
     g.lay = 2 if host else ((1 if step == 16 else 2 if step == 12 else 0) if tuple(offs) == (0, 4, 8) else 0)
     return g
 
@@ -256,7 +257,7 @@ def bins_of(xyz, g):
 
 
 def staging(xyz, g):
-    """What k_rt_part stages: per tile the records (own + halo copies, rt_tiles csrc/ror.hip:158), per point its own
+    """What k_rt_part stages: per tile the records (own + halo copies, rt_tiles csrc/ror.hip:139), per point its own
     tile and the number of its copies, per bin the point count. Only the binned points of xyz are returned."""
     m = binned(xyz, g)
     p = xyz[m]

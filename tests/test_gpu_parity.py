@@ -341,7 +341,7 @@ def test_dense_patches_overflow_the_lds_row_ring():
 
 
 def test_big_tile_after_frames_without_one_on_the_same_handle():
-    """The big-tile ROR kernels are skipped on frames whose largest tile fits LDS (seedgen.hip ror_stage: the
+    """The big-tile ROR kernels are skipped on frames whose largest tile fits LDS (ror_stage.hip ror_stage: the
     peeked tile maximum) and on guessed frames of a handle that never needed them; a guessed frame that then
     finds a big tile sets overflow bit 2 and is redone with them (ror_collect). Sequence on one handle:
     spread extra points (no big tile, fixes the staging guess) -> dense patches (the guessed frame's redo)

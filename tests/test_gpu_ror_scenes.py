@@ -1,4 +1,4 @@
-"""csrc/ror.hip and the ROR parts of csrc/seedgen.hip on the designed clouds of tests/ror_scenes.py: the raw raster
+"""csrc/ror.hip and csrc/ror_stage.hip on the designed clouds of tests/ror_scenes.py: the raw raster
 (debug_grid) bit for bit, n_clipped, n_input and n_ror_read against the oracle, then the rest of the frame. Each scene
 forces a compare rule or a branch that orchard clouds reach by accident at best; tests/test_ror_scenes_cpu.py asserts,
 without a GPU, that it does and that the oracle equals an independent numpy reference on it."""

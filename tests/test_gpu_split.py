@@ -1,4 +1,4 @@
-"""Host cloud split at upload (seedgen.hip upload_pack, aos_ctx::CloudSplit).
+"""Host cloud split at upload (cloud_upload.hip upload_pack, aos_ctx::CloudSplit).
 
 Only the points inside the ROR stage's binned box for the polygon current at upload time cross PCIe on the
 frame's path; the others stay in pinned host memory and are copied behind them when a later frame's box is

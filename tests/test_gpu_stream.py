@@ -72,7 +72,7 @@ def test_stream_custom_layout_and_non_dense_scan():
 def test_stream_c2_map_20_scans_incremental_equals_full_reprocessing():
     """BASELINE configs[4] at full size: the C2 map (10 M points) then 20 scans of 1 M points. From the
     second frame on each append only partitions the scan and recounts the tiles it reached (the
-    incremental ROR, seedgen.hip ror_stage_append), and its first thinning batch is a replayed hipGraph;
+    incremental ROR, ror_stage.hip ror_stage_append), and its first thinning batch is a replayed hipGraph;
     the reference handle reprocesses the whole concatenated cloud with plain launches. Every frame must be
     equal (grids, T, counts, rows, seeds), the GvdGraph every fourth scan; the frames after 5 and 20 scans
     must match the oracle's SHA-256 fixtures (tests/golden/c4_stream_sha256.json), and on the last frame

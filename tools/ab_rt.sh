@@ -1,6 +1,6 @@
 #!/bin/bash
-# A/B timing of ROR tile-walk variants (libaos_gpu_<v>.so built with DEFS=-DAOS_RT_VARIANT=<v>):
-# device-resident C2 bench, ROR sub-stage times from the HIP events. Timing only: variants 1/2 are wrong.
+# A/B timing of ROR tile-walk builds (libaos_gpu_<v>.so, e.g. of an edited ror.hip; VARIANTS names the suffixes):
+# device-resident C2 bench, ROR sub-stage times from the HIP events. Timing only: no parity check runs here.
 set -e
 export TMPDIR=/tmp
 mkdir -p gpurun_out

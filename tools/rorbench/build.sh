@@ -1,5 +1,5 @@
 #!/bin/bash
-# Builds tools/rorbench/rorbench[_<tag>] (DEFS passed through, e.g. DEFS=-DAOS_RT_VARIANT=1 TAG=_v1).
+# Builds tools/rorbench/rorbench[_<tag>] (TAG names a second build, e.g. of an edited ror.hip; DEFS passed through).
 set -e
 D=$(dirname "$0")
 gcc -O2 -fPIC -ffp-contract=off -c "$D/../orchard_gen.c" -o /tmp/orchard_gen_rb.o

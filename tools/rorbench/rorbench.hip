@@ -1,6 +1,6 @@
 // ROR-stage microbenchmark (a1-a4 only): the C2 synthetic cloud, the tile walk of ror.hip compiled in,
-// each pass timed with HIP events over several frames; prints the raster popcount and kept count so
-// variants (-DAOS_RT_VARIANT=..., tile / LDS constants) can be checked against each other.
+// each pass timed with HIP events over several frames; prints the raster popcount, kept count and raster hash
+// so that two builds of the tile walk can be checked against each other.
 // Build: tools/rorbench/build.sh   Run: tools/rorbench/rorbench [grid_n] [n_points] [frames] [step: 16 | 12]
 // [flush_mb: overwrite this many MB between frames, so the cloud and the staged array start cold as in a
 // product frame (MALL 256 MB); 0: warm, the previous frame's lines still cached]
@@ -121,8 +121,8 @@ int main(int argc, char **argv) {
     int *d_H = nullptr, *d_tot = nullptr; float4 *d_staged = nullptr, *d_scr = nullptr;
     unsigned long long *d_lb = nullptr; size_t cap_lb = 0;
     const int pretouch = getenv("RORBENCH_PRETOUCH") ? atoi(getenv("RORBENCH_PRETOUCH")) : 0;
-    unsigned long long *d_cnt; uint64_t *d_bits; int *d_big = nullptr; size_t cap_big = 0;
-    AOS_HIP(hipMalloc(&d_cnt, 8 * (kRorCounters + 2)));
+    RorCounters *d_cnt; uint64_t *d_bits; int *d_big = nullptr; size_t cap_big = 0;
+    AOS_HIP(hipMalloc(&d_cnt, sizeof(RorCounters)));
     AOS_HIP(hipMalloc(&d_bits, 8ull * WW * H));
     size_t cap_H = 0, cap_staged = 0, cap_t = 0;
     double acc[6] = {0, 0, 0, 0, 0, 0};
@@ -140,8 +140,8 @@ int main(int argc, char **argv) {
             AOS_HIP(hipMalloc(&d_lb, 8 * words + 64)); AOS_HIP(hipMemset(d_lb, 0, 8 * words + 64)); cap_lb = words;
         }
         const LookBack lb{d_lb, reinterpret_cast<unsigned *>(d_lb + cap_lb), (unsigned)(f + 1),
-                          reinterpret_cast<int *>(d_cnt + kRorCounters + 1)};
-        AOS_HIP(hipMemsetAsync(d_cnt, 0, 8 * (kRorCounters + 2), s));
+                          reinterpret_cast<int *>(&d_cnt->st.flags)};
+        AOS_HIP(hipMemsetAsync(d_cnt, 0, sizeof(RorCounters), s));
         AOS_HIP(hipMemsetAsync(d_bits, 0, 8ull * WW * H, s));
         if (d_flush) AOS_HIP(hipMemsetAsync(d_flush, f & 0xff, (size_t)flush_mb << 20, s));
         if (pretouch && d_staged) {   // outside the timed stage: in the product it would overlap the upload
@@ -156,14 +156,14 @@ int main(int argc, char **argv) {
             if (pstep == 12) rt_part<false, 2>(L, d_H, nullptr, G, nullptr, own, s);
             else rt_part<false, 1>(L, d_H, nullptr, G, nullptr, own, s);
             AOS_HIP(hipEventRecord(e[6], s));
-            ColScan C{d_H, d_ts, own, d_cnt + kRorCounters, nt, G, (G + kColRows - 1) / kColRows, (nt + kColTB - 1) / kColTB, lb};
+            ColScan C{d_H, d_ts, own, &d_cnt->st, nt, G, (G + kColRows - 1) / kColRows, (nt + kColTB - 1) / kColTB, lb};
             k_rt_colscan<<<C.ng * C.ntb, kColTB, 0, s>>>(C);
             AOS_HIP(hipEventRecord(e[1], s));
         }
         int total = 0;
         unsigned long long own = 0;
         AOS_HIP(hipMemcpyAsync(&total, d_ts + nt, 4, hipMemcpyDeviceToHost, s));
-        AOS_HIP(hipMemcpyAsync(&own, d_cnt + kRorCounters, 8, hipMemcpyDeviceToHost, s));
+        AOS_HIP(hipMemcpyAsync(&own, &d_cnt->st.binned, 8, hipMemcpyDeviceToHost, s));
         AOS_HIP(hipStreamSynchronize(s));
         est = (double)own;
         if ((size_t)total > cap_staged) {
@@ -171,12 +171,12 @@ int main(int argc, char **argv) {
             AOS_HIP(hipMalloc(&d_staged, 16ull * total)); AOS_HIP(hipMalloc(&d_scr, 16ull * total)); cap_staged = total;
         }
         L.staged_cap = (int)cap_staged;
-        L.overflow = reinterpret_cast<int *>(d_cnt + kRorCounters + 1);
+        L.overflow = reinterpret_cast<int *>(&d_cnt->st.flags);
         AOS_HIP(hipEventRecord(e[3], s));
         launch_rt_scatter(L, d_H, d_ts, G, d_staged, s);
         AOS_HIP(hipEventRecord(e[4], s));
         if (rt_bigbins_ints(L) > cap_big) { if (d_big) AOS_HIP(hipFree(d_big)); cap_big = rt_bigbins_ints(L); AOS_HIP(hipMalloc(&d_big, 4 * cap_big)); }
-        launch_rt_ror(L, d_ts, d_staged, d_scr, d_big, d_bits, d_cnt, nullptr, nullptr, s);
+        launch_rt_ror(L, d_ts, d_staged, d_scr, d_big, d_bits, d_cnt->kept, nullptr, nullptr, s);
         AOS_HIP(hipEventRecord(e[5], s));
         AOS_HIP(hipStreamSynchronize(s));
         float t[6];
@@ -191,12 +191,12 @@ int main(int argc, char **argv) {
             std::vector<uint64_t> bits((size_t)WW * H);
             std::vector<unsigned long long> cnt(kRorCounters);
             AOS_HIP(hipMemcpy(bits.data(), d_bits, 8 * bits.size(), hipMemcpyDeviceToHost));
-            AOS_HIP(hipMemcpy(cnt.data(), d_cnt, 8 * kRorCounters, hipMemcpyDeviceToHost));
+            AOS_HIP(hipMemcpy(cnt.data(), d_cnt->kept, sizeof(d_cnt->kept), hipMemcpyDeviceToHost));
             unsigned long long pc = 0, kept = 0, hsh = 1469598103934665603ull;
             for (uint64_t w : bits) { pc += __builtin_popcountll(w); hsh = (hsh ^ w) * 1099511628211ull; }
             for (auto v : cnt) kept += v;
             unsigned long long err = 0;
-            AOS_HIP(hipMemcpy(&err, d_cnt + kRorCounters + 1, 8, hipMemcpyDeviceToHost));
+            AOS_HIP(hipMemcpy(&err, &d_cnt->st.flags, 8, hipMemcpyDeviceToHost));
             printf("grid %dx%d n %llu TB %d tiles %d G %d staged %d binned %llu | raster cells %llu kept %llu hash %016llx err %llu\n", W, H,
                    (unsigned long long)n, L.TB, L.ntiles, G, total, own, pc, kept, hsh, err);
         }
