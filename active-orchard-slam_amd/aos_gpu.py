@@ -125,6 +125,11 @@ class PathOut(ctypes.Structure):
                 ("poses", P(c_d)), ("trimmed_from", c_i), ("ms_plan", c_f)]
 
 
+class LinearPathOut(ctypes.Structure):
+    _fields_ = [("published", c_i), ("long_distance", c_i), ("n_breakpoints", c_i), ("breakpoints", P(c_i)),
+                ("n_poses", c_i), ("poses", P(c_d)), ("n_split_searches", c_i), ("ms_linearize", c_f)]
+
+
 def path_query(initial_waypoint_reached=True, initial_waypoint=(8.0, 0.0), target=-1, saved_target=None, previous=-1,
                current=None, exploration_completed=False) -> PathQuery:
     """aos_path_gen_node state when a graph arrives (aos_path_query)."""
@@ -254,6 +259,7 @@ def lib():
         L.aos_tiled_seedgen_process.argtypes = [c_vp, P(Comm), c_i, c_i, c_i, P(CloudView), c_i, P(SeedGenOut)]
         L.aos_tiled_stats_get.argtypes = [c_vp, P(TiledStats)]
         L.aos_path_plan.argtypes = [c_vp, P(PathGraph), c_vp, c_i, P(GridInfo), P(PathQuery), P(PathOut)]
+        L.aos_path_linearize.argtypes = [c_vp, c_vp, c_i, P(LinearPathOut)]
         L.aos_group_create.argtypes = [P(Params), P(c_i), c_i, c_i, P(c_vp)]
         L.aos_group_destroy.argtypes = [c_vp]
         L.aos_group_set_polygon.argtypes = [c_vp, c_vp, c_u]
@@ -514,6 +520,21 @@ class Ctx:
                                    ctypes.byref(gi) if gi is not None else None, ctypes.byref(q), ctypes.byref(o)))
         del keep
         return _path_dict(o)
+
+    def path_linearize(self, poses=None) -> dict:
+        """aos_path_linearization_node's /aos/path -> /plan (aos_path_linearize). poses: (n, 4) x, y, qz, qw;
+        None: the poses of this handle's last path_plan (the fused form)."""
+        o = LinearPathOut()
+        if poses is None:
+            _check(lib().aos_path_linearize(self.h, None, 0, ctypes.byref(o)))
+        else:
+            a = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4)
+            buf = a if len(a) else np.zeros(4)   # (an empty path is an array with no poses, not the fused form)
+            _check(lib().aos_path_linearize(self.h, buf.ctypes.data, len(a), ctypes.byref(o)))
+        return {"published": o.published, "long_distance": o.long_distance,
+                "breakpoints": _arr(o.breakpoints, o.n_breakpoints, np.int32),
+                "poses": _arr(o.poses, 4 * o.n_poses, np.float64).reshape(-1, 4),
+                "n_split_searches": o.n_split_searches, "ms": o.ms_linearize}
 
     def cloud_prefetch(self, cloud, n_points: int | None = None, point_step=16, offs=(0, 4, 8), is_dense=True) -> None:
         """Start uploading a host PointCloud2 for the next seedgen() of the same array (aos_cloud_prefetch)."""

@@ -139,9 +139,18 @@ struct PathState {
     // outputs
     std::vector<int32_t> cluster_ids, cluster_nodes, waypoint_nodes, node_path;
     std::vector<double> waypoints_xy, poses;
+    bool planned = false;   // a plan has filled the outputs (aos_path_linearize's fused form reads poses)
 };
 
 void free_path_state(void *p) { delete static_cast<PathState *>(p); }
+
+bool path_last_poses(const void *path_state, const double **poses, int *n) {
+    const PathState *S = static_cast<const PathState *>(path_state);
+    if (!S || !S->planned) return false;
+    *poses = S->poses.data();
+    *n = (int)(S->poses.size() / 4);
+    return true;
+}
 
 namespace {
 
@@ -565,6 +574,7 @@ void aos_ctx::run_path_plan(const aos_path_graph *graph, const int8_t *skeleton,
     S.node_path.assign(pl.best.begin(), pl.best.end());
     S.poses.clear();
     for (const auto &p : pl.path) { S.poses.push_back(p.x); S.poses.push_back(p.y); S.poses.push_back(p.qz); S.poses.push_back(p.qw); }
+    S.planned = true;
     std::memset(&out, 0, sizeof(out));
     out.status = pl.status;
     out.target_waypoint_index = pl.target;

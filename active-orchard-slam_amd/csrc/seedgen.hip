@@ -36,6 +36,8 @@ void aos_ctx::release() {
         if (sp->copied) { (void)hipEventSynchronize(sp->copied); (void)hipEventDestroy(sp->copied); sp->copied = nullptr; }
     free_path_state(path_state);   // (a void * owner: path.hip's PathState)
     path_state = nullptr;
+    free_lin_state(lin_state);     // (linearize.hip's LinState)
+    lin_state = nullptr;
     for (auto &lp : lanes) {
         markers_wait(lp->gs, false);
         lp->gs.cells.reset();

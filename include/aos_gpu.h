@@ -431,6 +431,32 @@ typedef struct aos_path_out {
 int aos_path_plan(aos_ctx *ctx, const aos_path_graph *graph, const int8_t *skeleton, int skeleton_on_device,
                   const aos_grid_info *info, const aos_path_query *query, aos_path_out *out);
 
+/* ---------------------------------------------------------------------------------------------
+ * /aos/path -> /plan (aos_path_linearization_node): the path the controller drives on.
+ * At most 4 straight segments fitted by regression (10 when the path ends at the origin), resampled at 5 cm.
+ * aos_path_linearize <- AosPathLinearizationNode::pathCallback + convertToLinearSegments
+ *                       src/aos_path_linearization_node.cpp:372-395, 248-370
+ * The node's 1 Hz republish timer, stamps and header copies stay in the wrapper.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct aos_linear_path_out {
+    int32_t published;        /* 0: empty input (pathCallback returns, :373-375)                     */
+    int32_t long_distance;    /* last pose within 1e-6 of (0, 0) on both axes: 10 segments, else 4    */
+    int32_t n_breakpoints; const int32_t *breakpoints;  /* input indices the output is drawn through,
+                                 ascending, incl. 0 and n - 1; every index for 2 <= n <= 4; empty for n <= 1 */
+    int32_t n_poses; const double *poses;               /* x, y, qz, qw per /plan pose (z = 0)        */
+    int32_t n_split_searches; /* findBestSplitPoint calls (each one kernel launch)                    */
+    float ms_linearize;
+} aos_linear_path_out;
+/* poses: x, y, qz, qw per /aos/path pose, the layout of aos_path_out.poses (z = 0, qx = qy = 0). poses = NULL with
+ * n_poses = 0 is the fused form: the poses of the last aos_path_plan on this handle (AOS_E_STATE if none has run;
+ * after a "Failed" plan, which holds no poses: status 0 with published = 0); that plan's arrays stay valid and
+ * unchanged. The outputs are library-owned, in buffers of their own, valid until the next aos_path_linearize on the
+ * handle or aos_destroy. AOS_E_INVALID: a null out, a negative count, a null array with a count above 0,
+ * n_poses > 65536, a non-finite x or y, a segment longer than 2^22 x 0.05 m or an output above 2^22 poses (bounded
+ * as 1 + the sum over the segments of floor(length / 0.05) + 1): the node casts floor(distance / 0.05) to int,
+ * which is undefined there. */
+int aos_path_linearize(aos_ctx *ctx, const double *poses, int32_t n_poses, aos_linear_path_out *out);
+
 /* Diagnostics: copy an internal device grid of the last frame to host as int8 {0,100}.
  * which: "raster", "inflated", "opened", "skeleton_frameless". */
 int aos_debug_grid(aos_ctx *ctx, const char *which, int8_t *dst, uint64_t capacity);
