@@ -130,6 +130,15 @@ class LinearPathOut(ctypes.Structure):
                 ("n_poses", c_i), ("poses", P(c_d)), ("n_split_searches", c_i), ("ms_linearize", c_f)]
 
 
+class ClearanceOut(ctypes.Structure):
+    _fields_ = [("info", GridInfo), ("n_occupied", c_u64), ("max_d2", c_u), ("d2_device", c_vp), ("num_nodes", c_i),
+                ("num_edges", c_i), ("node_d2", P(c_u)), ("edge_d2", P(c_u)), ("node_clearances", P(c_f)),
+                ("edge_clearances", P(c_f)), ("ms_field", c_f), ("ms_graph", c_f)]
+
+
+D2_NONE = 0xFFFFFFFF
+
+
 def path_query(initial_waypoint_reached=True, initial_waypoint=(8.0, 0.0), target=-1, saved_target=None, previous=-1,
                current=None, exploration_completed=False) -> PathQuery:
     """aos_path_gen_node state when a graph arrives (aos_path_query)."""
@@ -260,6 +269,9 @@ def lib():
         L.aos_tiled_stats_get.argtypes = [c_vp, P(TiledStats)]
         L.aos_path_plan.argtypes = [c_vp, P(PathGraph), c_vp, c_i, P(GridInfo), P(PathQuery), P(PathOut)]
         L.aos_path_linearize.argtypes = [c_vp, c_vp, c_i, P(LinearPathOut)]
+        L.aos_gvd_clearance.argtypes = [c_vp, P(PathGraph), c_vp, c_i, P(GridInfo), P(ClearanceOut)]
+        L.aos_clearance_field_copy.argtypes = [c_vp, c_vp, c_u64]
+        L.aos_clearance_points.argtypes = [c_vp, c_vp, c_i, c_vp, c_vp]
         L.aos_group_create.argtypes = [P(Params), P(c_i), c_i, c_i, P(c_vp)]
         L.aos_group_destroy.argtypes = [c_vp]
         L.aos_group_set_polygon.argtypes = [c_vp, c_vp, c_u]
@@ -535,6 +547,56 @@ class Ctx:
                 "breakpoints": _arr(o.breakpoints, o.n_breakpoints, np.int32),
                 "poses": _arr(o.poses, 4 * o.n_poses, np.float64).reshape(-1, 4),
                 "n_split_searches": o.n_split_searches, "ms": o.ms_linearize}
+
+    def gvd_clearance(self, graph: dict | None = None, grid=None, info: dict | None = None,
+                      on_device: bool = False) -> dict:
+        """The exact distance field over `grid`'s occupied cells (== 100) and the clearances of the graph's nodes and
+        edges (aos_gvd_clearance). graph None: this handle's last GVD graph (only "nodes" and "edges" of a dict are
+        read); grid None: the skeleton that graph was built on; else an int8 array, or a device pointer with
+        on_device, and info = {"origin", "resolution", "width", "height"}."""
+        gs, keep = None, None
+        if graph is not None:
+            nodes = np.ascontiguousarray(graph["nodes"], dtype=np.float64).reshape(-1)
+            edges = np.ascontiguousarray(graph["edges"], dtype=np.int32).reshape(-1)
+            gs = PathGraph()
+            gs.num_nodes, gs.nodes_xy = nodes.size // 2, nodes.ctypes.data_as(P(c_d))
+            gs.num_edges, gs.edges = edges.size // 2, edges.ctypes.data_as(P(c_i))
+            keep = (nodes, edges)
+        gi, gp = None, None
+        if grid is not None:
+            gi = GridInfo(info["origin"][0], info["origin"][1], info["resolution"], info["width"], info["height"])
+            if on_device:
+                gp = c_vp(int(grid))
+            else:
+                keep = (keep, np.ascontiguousarray(grid, dtype=np.int8).reshape(-1))
+                gp = c_vp(keep[1].ctypes.data or 1)   # (an empty grid is still a grid, not the NULL form)
+        o = ClearanceOut()
+        _check(lib().aos_gvd_clearance(self.h, ctypes.byref(gs) if gs is not None else None, gp, int(on_device),
+                                       ctypes.byref(gi) if gi is not None else None, ctypes.byref(o)))
+        del keep
+        self._clear_shape = (o.info.height, o.info.width)
+        nn, ne = o.num_nodes, o.num_edges
+        return {"origin": (o.info.origin_x, o.info.origin_y), "resolution": o.info.resolution, "width": o.info.width,
+                "height": o.info.height, "n_occupied": o.n_occupied, "max_d2": o.max_d2, "d2_device": o.d2_device,
+                "node_d2": _arr(o.node_d2, nn, np.uint32), "edge_d2": _arr(o.edge_d2, ne, np.uint32),
+                "node_clearances": _arr(o.node_clearances, nn, np.float32),
+                "edge_clearances": _arr(o.edge_clearances, ne, np.float32),
+                "ms": {"field": o.ms_field, "graph": o.ms_graph}}
+
+    def clearance_field(self) -> np.ndarray:
+        """The last gvd_clearance's field as a (height, width) uint32 array (aos_clearance_field_copy)."""
+        out = np.empty(getattr(self, "_clear_shape", (0, 0)), np.uint32)
+        _check(lib().aos_clearance_field_copy(self.h, out.ctypes.data or None, out.size))
+        return out
+
+    def clearance_points(self, xy) -> tuple:
+        """(d2, metres) of points (n, 2) against the last gvd_clearance's field (aos_clearance_points)."""
+        a = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        n = len(a)
+        d2, m = np.empty(n, np.uint32), np.empty(n, np.float32)
+        _check(lib().aos_clearance_points(self.h, a.ctypes.data if n else None, n, d2.ctypes.data if n else None,
+                                          m.ctypes.data if n else None))
+        return d2, m
 
     def cloud_prefetch(self, cloud, n_points: int | None = None, point_step=16, offs=(0, 4, 8), is_dense=True) -> None:
         """Start uploading a host PointCloud2 for the next seedgen() of the same array (aos_cloud_prefetch)."""

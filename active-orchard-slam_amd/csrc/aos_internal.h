@@ -215,6 +215,7 @@ void free_path_state(void *p);   // path.hip
 // the poses (x, y, qz, qw) of the last aos_path_plan on the state (none after "Failed"); false: no plan has run
 bool path_last_poses(const void *path_state, const double **poses, int *n);   // path.hip
 void free_lin_state(void *p);    // linearize.hip
+void free_clear_state(void *p);  // clearance.hip
 
 TilePlan make_tile_plan(const FrameGeom &g, float margin, int tiles_x, int tiles_y, int rank);
 

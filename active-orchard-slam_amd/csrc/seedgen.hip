@@ -38,6 +38,8 @@ void aos_ctx::release() {
     path_state = nullptr;
     free_lin_state(lin_state);     // (linearize.hip's LinState)
     lin_state = nullptr;
+    free_clear_state(clear_state); // (clearance.hip's ClearState)
+    clear_state = nullptr;
     for (auto &lp : lanes) {
         markers_wait(lp->gs, false);
         lp->gs.cells.reset();

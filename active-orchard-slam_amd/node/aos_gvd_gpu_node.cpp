@@ -33,6 +33,9 @@ class AosGvdGpuNode : public rclcpp::Node {
         aos_params p;
         aos_default_params(&p);
         p.max_graph_publish_rate = rate_;
+        // false (default): GvdGraph.edge_clearances as the reference publishes it, all zero (min_clearance_m is never
+        // computed, gvd:466); true: the edges' real clearance in metres from aos_gvd_clearance
+        fill_edge_clearances_ = declare_parameter("fill_edge_clearances", false);
         if (aos_create(&p, declare_parameter<int>("gpu_device", 0), &ctx_) != AOS_OK) throw std::runtime_error(aos_last_error());
         // markers only for the published frames: publish_markers asks for them (computed on demand), as
         // publishMarkers runs inside the publish throttle (gvd:306-314)
@@ -98,6 +101,13 @@ class AosGvdGpuNode : public rclcpp::Node {
         g.edges.assign(o.edges, o.edges + 2 * o.num_edges);
         g.edge_lengths.assign(o.edge_lengths, o.edge_lengths + o.num_edges);
         g.edge_clearances.assign(o.edge_clearances, o.edge_clearances + o.num_edges);
+        if (fill_edge_clearances_) {   // (after the copies above: the handle's graph and the skeleton it was built on)
+            aos_clearance_out cl{};
+            if (aos_gvd_clearance(ctx_, nullptr, nullptr, 0, nullptr, &cl) == AOS_OK && cl.num_edges == o.num_edges)
+                g.edge_clearances.assign(cl.edge_clearances, cl.edge_clearances + cl.num_edges);
+            else
+                RCLCPP_ERROR(get_logger(), "edge clearances not filled: %s", aos_last_error());
+        }
         pub_graph_->publish(g);
         publish_markers(g.header, o);
         last_ = now;
@@ -224,6 +234,7 @@ class AosGvdGpuNode : public rclcpp::Node {
 
     aos_ctx *ctx_ = nullptr;
     double rate_ = 10.0;
+    bool fill_edge_clearances_ = false;
     std::chrono::steady_clock::time_point last_ = std::chrono::steady_clock::now();   // gvd:80
     std::vector<double> seeds_, rows_;
     nav_msgs::msg::OccupancyGrid::SharedPtr skel_;

@@ -457,6 +457,51 @@ typedef struct aos_linear_path_out {
  * which is undefined there. */
 int aos_path_linearize(aos_ctx *ctx, const double *poses, int32_t n_poses, aos_linear_path_out *out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Clearances of the GvdGraph (GvdGraph.msg float32[] edge_clearances). The reference declares the field and never
+ * computes it: EdgeRecord::min_clearance_m stays 0 (gvd:466, :1000-1006, :1637), and aos_gvd_out.edge_clearances
+ * keeps that zero. aos_gvd_clearance computes the real value from an exact distance field.
+ *  - Occupied cell: the byte is 100 (the test of edgePassesThroughOccupiedPixels and trimPathNearOccupiedRegions);
+ *    every other value is free.
+ *  - Field: d2[y * width + x] = min over occupied (cx, cy) of (x - cx)^2 + (y - cy)^2, uint32 in cell units;
+ *    AOS_D2_NONE everywhere when no cell is occupied. width, height <= 16384, so d2 < 2^29.
+ *  - A point's cell: fx = (px - origin_x) / res, fy likewise (res = (double)info.resolution); the point has a cell
+ *    iff -1 < fx < width, -1 < fy < height and the truncation toward zero of (fx, fy) lies in the grid.
+ *  - node_d2 = d2 at the node's cell. edge_d2 = the minimum of d2 over the samples of edgePassesThroughOccupiedPixels
+ *    (gvd:320-359) from node edges[2k] to node edges[2k + 1] that have a cell: num = (int)(len / (res * 0.5)) + 1,
+ *    samples s + (t * u) * len for t = i / num, i = 0 .. num (t = 1 at i = num); an edge shorter than 1e-6 has the
+ *    sample s; num out of int range: no samples. AOS_D2_NONE: no sample has a cell, or the field is empty.
+ *  - Metres: (float)(sqrt((double)d2) * res), +inf for AOS_D2_NONE. The distance runs between cell centres: it is
+ *    quantised to the grid on purpose (a point takes its cell's value; no sub-cell distances).
+ * graph: NULL = this handle's last GVD graph; only nodes_xy, num_nodes, edges and num_edges are read. grid: int8
+ * bytes, host memory (grid_on_device = 0) or device memory on the handle's GPU (1), with `info`; NULL = the skeleton
+ * that graph was built on, with its info (AOS_E_STATE if there was no GVD call, or a later seed-gen frame replaced
+ * it). AOS_E_INVALID: a null out, a negative count, a null array behind a positive count, a grid without info, width
+ * or height above 16384, a resolution that is not finite or <= 0, a non-finite node coordinate, an edge index
+ * outside [0, num_nodes). width * height = 0: status 0, n_occupied 0, d2_device NULL, every clearance AOS_D2_NONE
+ * (+inf). Every call recomputes its field. The outputs are library-owned and valid until the next aos_gvd_clearance
+ * on the handle or aos_destroy.
+ * ------------------------------------------------------------------------------------------- */
+#define AOS_D2_NONE 0xFFFFFFFFu
+typedef struct aos_clearance_out {
+    aos_grid_info info;
+    uint64_t n_occupied;
+    uint32_t max_d2;                                 /* over the field; AOS_D2_NONE if n_occupied == 0        */
+    const uint32_t *d2_device;                       /* width * height words on the handle's GPU              */
+    int32_t num_nodes, num_edges;
+    const uint32_t *node_d2, *edge_d2;               /* host, library-owned                                   */
+    const float *node_clearances, *edge_clearances;  /* metres; what a wrapper puts into GvdGraph.msg         */
+    float ms_field, ms_graph;                        /* device time of the field passes / the sampling        */
+} aos_clearance_out;
+int aos_gvd_clearance(aos_ctx *ctx, const aos_path_graph *graph, const int8_t *grid, int grid_on_device,
+                      const aos_grid_info *info, aos_clearance_out *out);
+/* The last aos_gvd_clearance's field copied to host memory. AOS_E_STATE before any field exists; AOS_E_INVALID for
+ * a capacity_cells below width * height. */
+int aos_clearance_field_copy(aos_ctx *ctx, uint32_t *dst, uint64_t capacity_cells);
+/* d2 and metres of n points (x, y) against the last aos_gvd_clearance's field, by the node rule (e.g. /plan poses).
+ * Either output may be null. AOS_E_STATE before any field exists; a non-finite point has no cell. */
+int aos_clearance_points(aos_ctx *ctx, const double *xy, int32_t n, uint32_t *d2_out, float *metres_out);
+
 /* Diagnostics: copy an internal device grid of the last frame to host as int8 {0,100}.
  * which: "raster", "inflated", "opened", "skeleton_frameless". */
 int aos_debug_grid(aos_ctx *ctx, const char *which, int8_t *dst, uint64_t capacity);
