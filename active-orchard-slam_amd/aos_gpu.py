@@ -139,6 +139,23 @@ class ClearanceOut(ctypes.Structure):
 D2_NONE = 0xFFFFFFFF
 
 
+class RegionsOpts(ctypes.Structure):
+    _fields_ = [("min_component_cells", c_i), ("want_ridge_distance", c_i)]
+
+
+class RegionsOut(ctypes.Structure):
+    _fields_ = [("info", GridInfo), ("n_occupied", c_u64), ("n_sites", c_u64), ("n_ridge", c_u64),
+                ("n_components", ctypes.c_int64), ("n_regions", ctypes.c_int64), ("max_d2", c_u), ("site_device", c_vp),
+                ("region_device", c_vp), ("ridge_device", c_vp), ("ridge_d2_device", c_vp), ("num_nodes", c_i),
+                ("node_site", P(c_u)), ("node_region", P(c_i)), ("node_d2", P(c_u)), ("node_ridge_d2", P(c_u)),
+                ("node_ridge_offset", P(c_f)), ("ms_label", c_f), ("ms_field", c_f), ("ms_ridge", c_f), ("ms_graph", c_f)]
+
+
+SITE_NONE = 0xFFFFFFFF
+REGION_NONE = -1
+REGIONS_FIELDS = {"site": np.uint32, "region": np.int32, "ridge": np.int8, "ridge_d2": np.uint32}
+
+
 def path_query(initial_waypoint_reached=True, initial_waypoint=(8.0, 0.0), target=-1, saved_target=None, previous=-1,
                current=None, exploration_completed=False) -> PathQuery:
     """aos_path_gen_node state when a graph arrives (aos_path_query)."""
@@ -272,6 +289,9 @@ def lib():
         L.aos_gvd_clearance.argtypes = [c_vp, P(PathGraph), c_vp, c_i, P(GridInfo), P(ClearanceOut)]
         L.aos_clearance_field_copy.argtypes = [c_vp, c_vp, c_u64]
         L.aos_clearance_points.argtypes = [c_vp, c_vp, c_i, c_vp, c_vp]
+        L.aos_gvd_regions.argtypes = [c_vp, P(PathGraph), c_vp, c_i, P(GridInfo), c_vp, P(RegionsOpts), P(RegionsOut)]
+        L.aos_regions_field_copy.argtypes = [c_vp, ctypes.c_char_p, c_vp, c_u64]
+        L.aos_regions_points.argtypes = [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp]
         L.aos_group_create.argtypes = [P(Params), P(c_i), c_i, c_i, P(c_vp)]
         L.aos_group_destroy.argtypes = [c_vp]
         L.aos_group_set_polygon.argtypes = [c_vp, c_vp, c_u]
@@ -597,6 +617,67 @@ class Ctx:
         _check(lib().aos_clearance_points(self.h, a.ctypes.data if n else None, n, d2.ctypes.data if n else None,
                                           m.ctypes.data if n else None))
         return d2, m
+
+    def gvd_regions(self, graph: dict | None = None, grid=None, info: dict | None = None, on_device: bool = False,
+                    labels=None, min_component_cells: int = 0, want_ridge_distance: bool = False) -> dict:
+        """For every cell of `grid` the nearest site, its region, the ridge between the regions (the grid GVD) and, with
+        want_ridge_distance, the distance field to the ridge; the values at the graph's nodes (aos_gvd_regions). graph,
+        grid, info and on_device as in gvd_clearance. labels None: the sites are the occupied cells of the 8-connected
+        components with at least min_component_cells cells, labelled by their least cell index; else int32 labels per
+        cell (an array, or a device pointer with on_device): an occupied cell with a label >= 0 is a site."""
+        gs, keep = None, []
+        if graph is not None:
+            nodes = np.ascontiguousarray(graph["nodes"], dtype=np.float64).reshape(-1)
+            gs = PathGraph()
+            gs.num_nodes, gs.nodes_xy = nodes.size // 2, nodes.ctypes.data_as(P(c_d))
+            keep.append(nodes)
+        gi, gp, lp = None, None, None
+        if grid is not None:
+            gi = GridInfo(info["origin"][0], info["origin"][1], info["resolution"], info["width"], info["height"])
+            if on_device:
+                gp = c_vp(int(grid))
+            else:
+                keep.append(np.ascontiguousarray(grid, dtype=np.int8).reshape(-1))
+                gp = c_vp(keep[-1].ctypes.data or 1)   # (an empty grid is still a grid, not the NULL form)
+        if labels is not None:
+            if on_device:
+                lp = c_vp(int(labels))
+            else:
+                keep.append(np.ascontiguousarray(labels, dtype=np.int32).reshape(-1))
+                lp = c_vp(keep[-1].ctypes.data or 1)
+        opts = RegionsOpts(int(min_component_cells), int(bool(want_ridge_distance)))
+        o = RegionsOut()
+        _check(lib().aos_gvd_regions(self.h, ctypes.byref(gs) if gs is not None else None, gp, int(on_device),
+                                     ctypes.byref(gi) if gi is not None else None, lp, ctypes.byref(opts), ctypes.byref(o)))
+        del keep
+        self._regions_shape = (o.info.height, o.info.width)
+        nn = o.num_nodes
+        return {"origin": (o.info.origin_x, o.info.origin_y), "resolution": o.info.resolution, "width": o.info.width,
+                "height": o.info.height, "n_occupied": o.n_occupied, "n_components": o.n_components, "n_sites": o.n_sites,
+                "n_regions": o.n_regions, "n_ridge": o.n_ridge, "max_d2": o.max_d2, "site_device": o.site_device,
+                "region_device": o.region_device, "ridge_device": o.ridge_device, "ridge_d2_device": o.ridge_d2_device,
+                "node_site": _arr(o.node_site, nn, np.uint32), "node_region": _arr(o.node_region, nn, np.int32),
+                "node_d2": _arr(o.node_d2, nn, np.uint32), "node_ridge_d2": _arr(o.node_ridge_d2, nn, np.uint32),
+                "node_ridge_offset": _arr(o.node_ridge_offset, nn, np.float32),
+                "ms": {"label": o.ms_label, "field": o.ms_field, "ridge": o.ms_ridge, "graph": o.ms_graph}}
+
+    def regions_field(self, which: str) -> np.ndarray:
+        """A field of the last gvd_regions as a (height, width) array: "site" (uint32), "region" (int32), "ridge" (int8) or
+        "ridge_d2" (uint32) (aos_regions_field_copy)."""
+        out = np.empty(getattr(self, "_regions_shape", (0, 0)), REGIONS_FIELDS.get(which, np.uint32))
+        _check(lib().aos_regions_field_copy(self.h, which.encode(), out.ctypes.data or None, out.size))
+        return out
+
+    def regions_points(self, xy) -> dict:
+        """site, region, d2, ridge_d2 and ridge_offset (metres) of points (n, 2) against the last gvd_regions' fields
+        (aos_regions_points)."""
+        a = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        n = len(a)
+        r = {"site": np.empty(n, np.uint32), "region": np.empty(n, np.int32), "d2": np.empty(n, np.uint32),
+             "ridge_d2": np.empty(n, np.uint32), "ridge_offset": np.empty(n, np.float32)}
+        _check(lib().aos_regions_points(self.h, a.ctypes.data if n else None, n,
+                                        *[v.ctypes.data if n else None for v in r.values()]))
+        return r
 
     def cloud_prefetch(self, cloud, n_points: int | None = None, point_step=16, offs=(0, 4, 8), is_dense=True) -> None:
         """Start uploading a host PointCloud2 for the next seedgen() of the same array (aos_cloud_prefetch)."""

@@ -2,8 +2,8 @@
 // release() (seedgen.hip) stops the threads and destroys the streams and events first.
 // Methods by file: seedgen.hip the frame (release, run_seedgen*, the thinning driver, the grid copies, finish_frame,
 // debug_grid); cloud_upload.hip the cloud upload, the prefetch and the streaming map's ingest; ror_stage.hip the
-// ROR stage; tiled.hip the tiled frame; gvd_handle.hip the GVD; path.hip the planner (linearize.hip and clearance.hip
-// have no method: their state hangs off lin_state and clear_state).
+// ROR stage; tiled.hip the tiled frame; gvd_handle.hip the GVD; path.hip the planner (linearize.hip, clearance.hip
+// and regions.hip have no method: their state hangs off lin_state, clear_state and regions_state).
 #pragma once
 #include <array>
 #include <condition_variable>
@@ -237,6 +237,8 @@ struct aos_ctx {
     void *lin_state = nullptr;    // aos::LinState
     // ---- distance field and GvdGraph clearances (clearance.hip)
     void *clear_state = nullptr;  // aos::ClearState
+    // ---- nearest-obstacle regions and the grid GVD ridge (regions.hip)
+    void *regions_state = nullptr;  // aos::RegionsState
 
     // ---- cloud upload, prefetch and streaming map ingest (cloud_upload.hip)
     void set_cloud(const aos_cloud_view &v);

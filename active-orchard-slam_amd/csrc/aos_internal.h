@@ -216,6 +216,13 @@ void free_path_state(void *p);   // path.hip
 bool path_last_poses(const void *path_state, const double **poses, int *n);   // path.hip
 void free_lin_state(void *p);    // linearize.hip
 void free_clear_state(void *p);  // clearance.hip
+void free_regions_state(void *p);   // regions.hip
+// The distance field's buffers and launches (clearance.hip), shared with regions.hip, which runs them on its own
+// buffers: masks / up / down = the (64-row band, column) occupancy words and the nearest occupied row above / below
+// each band; g = the column distances; d2 = the field; stats = the occupied count (8 bytes) and the maximum.
+struct ClrFieldBufs { DevBuf masks, up, down, g, d2, stats; };
+void clr_launch_bands(ClrFieldBufs &B, const int8_t *d_grid, int W, int H, unsigned long long *n_occ, hipStream_t s);
+void clr_launch_field(ClrFieldBufs &B, const int8_t *d_grid, int W, int H, hipStream_t s);
 
 TilePlan make_tile_plan(const FrameGeom &g, float margin, int tiles_x, int tiles_y, int rank);
 

@@ -247,7 +247,8 @@ __global__ void __launch_bounds__(kClrTB) k_clr_sample(clr::Grid g, const uint32
 }
 
 struct ClearState {
-    DevBuf d_grid, d_masks, d_up, d_down, d_g, d_d2, d_nodes, d_edges, d_stats, d_pts;
+    ClrFieldBufs f;   // the field's scratch, the field (f.d2) and its statistics (f.stats)
+    DevBuf d_grid, d_nodes, d_edges, d_pts;
     PinnedBuf h_out, h_pts;
     std::vector<float> node_m, edge_m;
     hipEvent_t ev[3] = {};
@@ -261,6 +262,32 @@ struct ClearState {
 
 void free_clear_state(void *p) { delete static_cast<ClearState *>(p); }
 
+template <class T> static T *clr_dev(DevBuf &b, size_t n) { return static_cast<T *>(b.ensure(sizeof(T) * std::max<size_t>(n, 1))); }
+
+// the band words and the carries of d_grid (W, H >= 1); *n_occ += the occupied count (regions.hip shares these two)
+void clr_launch_bands(ClrFieldBufs &B, const int8_t *d_grid, int W, int H, unsigned long long *n_occ, hipStream_t s) {
+    const int nb = clr_cdiv(H, kClrBand);
+    auto *masks = clr_dev<unsigned long long>(B.masks, (size_t)nb * W);
+    int *up = clr_dev<int>(B.up, (size_t)nb * W), *down = clr_dev<int>(B.down, (size_t)nb * W);
+    k_clr_bands<<<dim3(clr_cdiv(W, kClrTB), nb), kClrTB, 0, s>>>(d_grid, W, H, masks, n_occ);
+    k_clr_carry<<<clr_cdiv(W, kClrTB), kClrTB, 0, s>>>(masks, W, nb, up, down);
+}
+
+// the three field passes on d_grid (W, H >= 1) into B.d2; B.stats: the occupied count (8 bytes), the maximum
+void clr_launch_field(ClrFieldBufs &B, const int8_t *d_grid, int W, int H, hipStream_t s) {
+    const size_t C = (size_t)W * H;
+    const int nb = clr_cdiv(H, kClrBand);
+    uint16_t *g = clr_dev<uint16_t>(B.g, C);
+    uint32_t *d2 = clr_dev<uint32_t>(B.d2, C);
+    char *st = clr_dev<char>(B.stats, 16);
+    AOS_HIP(hipMemsetAsync(st, 0, 16, s));
+    clr_launch_bands(B, d_grid, W, H, reinterpret_cast<unsigned long long *>(st), s);
+    k_clr_cols<<<dim3(clr_cdiv(W, kClrTB), nb), kClrTB, 0, s>>>(B.masks.as<unsigned long long>(), B.up.as<int>(),
+                                                                 B.down.as<int>(), W, H, g);
+    k_clr_rows<<<H, kClrTB, 0, s>>>(g, W, d2, reinterpret_cast<unsigned *>(st + 8));
+    AOS_HIP(hipGetLastError());
+}
+
 namespace {
 
 ClearState &clear_state(aos_ctx *c) {
@@ -268,26 +295,6 @@ ClearState &clear_state(aos_ctx *c) {
     ClearState &S = *static_cast<ClearState *>(c->clear_state);
     for (hipEvent_t &e : S.ev) if (!e) AOS_HIP(hipEventCreate(&e));
     return S;
-}
-
-template <class T> T *clr_dev(DevBuf &b, size_t n) { return static_cast<T *>(b.ensure(sizeof(T) * std::max<size_t>(n, 1))); }
-
-// the three field passes on d_grid (W, H >= 1) into S.d_d2; S.d_stats: the occupied count (8 bytes), the maximum
-void launch_field(ClearState &S, const int8_t *d_grid, int W, int H, hipStream_t s) {
-    const size_t C = (size_t)W * H;
-    const int nb = clr_cdiv(H, kClrBand);
-    auto *masks = clr_dev<unsigned long long>(S.d_masks, (size_t)nb * W);
-    int *up = clr_dev<int>(S.d_up, (size_t)nb * W), *down = clr_dev<int>(S.d_down, (size_t)nb * W);
-    uint16_t *g = clr_dev<uint16_t>(S.d_g, C);
-    uint32_t *d2 = clr_dev<uint32_t>(S.d_d2, C);
-    char *st = clr_dev<char>(S.d_stats, 16);
-    AOS_HIP(hipMemsetAsync(st, 0, 16, s));
-    const dim3 cg(clr_cdiv(W, kClrTB), nb);
-    k_clr_bands<<<cg, kClrTB, 0, s>>>(d_grid, W, H, masks, reinterpret_cast<unsigned long long *>(st));
-    k_clr_carry<<<clr_cdiv(W, kClrTB), kClrTB, 0, s>>>(masks, W, nb, up, down);
-    k_clr_cols<<<cg, kClrTB, 0, s>>>(masks, up, down, W, H, g);
-    k_clr_rows<<<H, kClrTB, 0, s>>>(g, W, d2, reinterpret_cast<unsigned *>(st + 8));
-    AOS_HIP(hipGetLastError());
 }
 
 int fail(int code, const std::string &msg) { set_error(msg); return code; }
@@ -373,12 +380,12 @@ extern "C" int aos_gvd_clearance(aos_ctx *c, const aos_path_graph *graph, const 
             if (nn) AOS_HIP(hipMemcpyAsync(d_nodes, nodes_xy, sizeof(double2) * (size_t)nn, hipMemcpyHostToDevice, c->stream));
             if (ne) AOS_HIP(hipMemcpyAsync(d_edges, edges, sizeof(int2) * (size_t)ne, hipMemcpyHostToDevice, c->stream));
             AOS_HIP(hipEventRecord(S.ev[0], c->stream));
-            launch_field(S, d_grid, S.g.W, S.g.H, c->stream);
+            clr_launch_field(S.f, d_grid, S.g.W, S.g.H, c->stream);
             AOS_HIP(hipEventRecord(S.ev[1], c->stream));
             const int nbn = clr_cdiv(nn, kClrTB), nbe = clr_cdiv(ne, kClrTB);
-            const char *st = S.d_stats.as<char>();
+            const char *st = S.f.stats.as<char>();
             k_clr_sample<<<std::max(1, nbn + nbe), kClrTB, 0, c->stream>>>(
-                S.g, S.d_d2.as<uint32_t>(), d_nodes, nn, d_edges, ne, nbn, h_node, h_edge,
+                S.g, S.f.d2.as<uint32_t>(), d_nodes, nn, d_edges, ne, nbn, h_node, h_edge,
                 reinterpret_cast<const unsigned long long *>(st), reinterpret_cast<const unsigned *>(st + 8), h_stats);
             AOS_HIP(hipGetLastError());
             AOS_HIP(hipEventRecord(S.ev[2], c->stream));
@@ -395,7 +402,7 @@ extern "C" int aos_gvd_clearance(aos_ctx *c, const aos_path_graph *graph, const 
         out->info = gi;
         out->n_occupied = (uint64_t)h_stats[0] | ((uint64_t)h_stats[1] << 32);
         out->max_d2 = out->n_occupied ? h_stats[2] : clr::kNone;
-        out->d2_device = C ? S.d_d2.as<uint32_t>() : nullptr;
+        out->d2_device = C ? S.f.d2.as<uint32_t>() : nullptr;
         out->num_nodes = nn; out->num_edges = ne;
         out->node_d2 = h_node; out->edge_d2 = h_edge;
         out->node_clearances = S.node_m.data(); out->edge_clearances = S.edge_m.data();
@@ -415,7 +422,7 @@ extern "C" int aos_clearance_field_copy(aos_ctx *c, uint32_t *dst, uint64_t capa
     try {
         DeviceScope dev_scope(c->device);
         if (C) {
-            AOS_HIP(hipMemcpyAsync(dst, S->d_d2.p, sizeof(uint32_t) * C, hipMemcpyDeviceToHost, c->stream));
+            AOS_HIP(hipMemcpyAsync(dst, S->f.d2.p, sizeof(uint32_t) * C, hipMemcpyDeviceToHost, c->stream));
             AOS_HIP(hipStreamSynchronize(c->stream));
         }
         return AOS_OK;
@@ -438,7 +445,7 @@ extern "C" int aos_clearance_points(aos_ctx *c, const double *xy, int32_t n, uin
             double2 *d_pts = clr_dev<double2>(S->d_pts, n);
             AOS_HIP(hipMemcpyAsync(d_pts, xy, sizeof(double2) * (size_t)n, hipMemcpyHostToDevice, c->stream));
             const int nbn = clr_cdiv(n, kClrTB);
-            k_clr_sample<<<nbn, kClrTB, 0, c->stream>>>(S->g, S->d_d2.as<uint32_t>(), d_pts, n, nullptr, 0, nbn, h, nullptr,
+            k_clr_sample<<<nbn, kClrTB, 0, c->stream>>>(S->g, S->f.d2.as<uint32_t>(), d_pts, n, nullptr, 0, nbn, h, nullptr,
                                                         nullptr, nullptr, nullptr);
             AOS_HIP(hipGetLastError());
             AOS_HIP(hipStreamSynchronize(c->stream));

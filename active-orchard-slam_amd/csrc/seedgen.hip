@@ -40,6 +40,8 @@ void aos_ctx::release() {
     lin_state = nullptr;
     free_clear_state(clear_state); // (clearance.hip's ClearState)
     clear_state = nullptr;
+    free_regions_state(regions_state); // (regions.hip's RegionsState)
+    regions_state = nullptr;
     for (auto &lp : lanes) {
         markers_wait(lp->gs, false);
         lp->gs.cells.reset();

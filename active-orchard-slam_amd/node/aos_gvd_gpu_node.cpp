@@ -36,6 +36,9 @@ class AosGvdGpuNode : public rclcpp::Node {
         // false (default): GvdGraph.edge_clearances as the reference publishes it, all zero (min_clearance_m is never
         // computed, gvd:466); true: the edges' real clearance in metres from aos_gvd_clearance
         fill_edge_clearances_ = declare_parameter("fill_edge_clearances", false);
+        // true: after each published graph, the grid GVD ridge of its skeleton (aos_gvd_regions: the ridge between the
+        // nearest-obstacle regions of the skeleton's components) goes out as an OccupancyGrid beside the graph
+        publish_ridge_grid_ = declare_parameter("publish_ridge_grid", false);
         if (aos_create(&p, declare_parameter<int>("gpu_device", 0), &ctx_) != AOS_OK) throw std::runtime_error(aos_last_error());
         // markers only for the published frames: publish_markers asks for them (computed on demand), as
         // publishMarkers runs inside the publish throttle (gvd:306-314)
@@ -61,6 +64,7 @@ class AosGvdGpuNode : public rclcpp::Node {
             [this](nav_msgs::msg::OccupancyGrid::SharedPtr m) { skel_ = m; process(); });   // gvd:173-177
         pub_graph_ = create_publisher<aos::msg::GvdGraph>("/gvd/graph", reliable);
         pub_markers_ = create_publisher<visualization_msgs::msg::MarkerArray>("/gvd/markers", reliable);
+        if (publish_ridge_grid_) pub_ridge_ = create_publisher<nav_msgs::msg::OccupancyGrid>("/gvd/ridge_grid", reliable);
     }
     ~AosGvdGpuNode() override { aos_destroy(ctx_); }
 
@@ -110,7 +114,26 @@ class AosGvdGpuNode : public rclcpp::Node {
         }
         pub_graph_->publish(g);
         publish_markers(g.header, o);
+        if (publish_ridge_grid_) publish_ridge(g.header);
         last_ = now;
+    }
+
+    // the ridge bytes (0 / 100) of the handle's graph's skeleton, with the skeleton's grid info
+    void publish_ridge(const std_msgs::msg::Header &h) {
+        aos_regions_out r{};
+        if (aos_gvd_regions(ctx_, nullptr, nullptr, 0, nullptr, nullptr, nullptr, &r) != AOS_OK) {
+            RCLCPP_ERROR(get_logger(), "ridge grid not published: %s", aos_last_error());
+            return;
+        }
+        nav_msgs::msg::OccupancyGrid m;
+        m.header = h;
+        m.info = skel_->info;
+        m.data.resize((size_t)r.info.width * r.info.height);
+        if (aos_regions_field_copy(ctx_, "ridge", m.data.data(), m.data.size()) != AOS_OK) {
+            RCLCPP_ERROR(get_logger(), "ridge grid not published: %s", aos_last_error());
+            return;
+        }
+        pub_ridge_->publish(m);
     }
 
     // publishMarkers gvd:1012-1591 (content from the library, styles as in the reference)
@@ -235,6 +258,8 @@ class AosGvdGpuNode : public rclcpp::Node {
     aos_ctx *ctx_ = nullptr;
     double rate_ = 10.0;
     bool fill_edge_clearances_ = false;
+    bool publish_ridge_grid_ = false;
+    rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>::SharedPtr pub_ridge_;
     std::chrono::steady_clock::time_point last_ = std::chrono::steady_clock::now();   // gvd:80
     std::vector<double> seeds_, rows_;
     nav_msgs::msg::OccupancyGrid::SharedPtr skel_;

@@ -502,6 +502,79 @@ int aos_clearance_field_copy(aos_ctx *ctx, uint32_t *dst, uint64_t capacity_cell
  * Either output may be null. AOS_E_STATE before any field exists; a non-finite point has no cell. */
 int aos_clearance_points(aos_ctx *ctx, const double *xy, int32_t n, uint32_t *d2_out, float *metres_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Nearest-obstacle regions and the grid GVD ridge. The reference approximates the ridge between the tree rows with
+ * point seeds (virtual, ray and endpoint seeds); aos_gvd_regions computes the ridge itself on the grid, so a caller
+ * can tell how far a graph node or a /plan pose lies from it. Every quantity is an integer: the definitions below fix
+ * every word of the result.
+ *  - Grid: int8 bytes with `info`; a cell is occupied iff its byte is 100. width, height <= 16384. The linear index
+ *    of cell (x, y) is i = y * width + x (< 2^28).
+ *  - Sites and labels, labels = NULL: the occupied cells are split into 8-connected components; a component's label
+ *    is the least linear index of its cells. With opts.min_component_cells > 1 the components with fewer cells are
+ *    dropped: their cells stay occupied and are not sites. n_occupied = the occupied cells, n_components = all
+ *    components, n_sites = the site cells, n_regions = the components kept.
+ *  - Sites and labels, labels given (int32[width * height], in the same kind of memory as grid, read only at occupied
+ *    cells): an occupied cell with label >= 0 is a site with that label; a negative label: not a site. Equal labels
+ *    on separate components are one region. min_component_cells > 1 with labels is AOS_E_INVALID. n_components and
+ *    n_regions are -1.
+ *  - Nearest site: site[c] = the linear index of the site cell s with the least pair (squared distance between the
+ *    centres of c and s in cells, linear index of s), compared lexicographically; AOS_SITE_NONE everywhere when there
+ *    is no site. A site cell is its own site. d2[c] is that squared distance (AOS_D2_NONE without a site): it follows
+ *    from site[c] and is not stored. max_d2 = its maximum (AOS_D2_NONE without a site). region[c] = the label of
+ *    site[c], or AOS_REGION_NONE.
+ *  - Ridge (the grid GVD; int8, 0 or 100): take every pair of 4-adjacent cells (c, n), n = (x + 1, y) or (x, y + 1),
+ *    whose regions are both not AOS_REGION_NONE and differ. The pair marks c if c is not a site cell; otherwise it
+ *    marks n if n is not a site cell; otherwise it marks neither. A cell is a ridge cell iff some pair marks it;
+ *    n_ridge = their count.
+ *  - Ridge distance (opts.want_ridge_distance != 0): ridge_d2 = the field of aos_gvd_clearance with the ridge cells
+ *    as the occupied cells; AOS_D2_NONE everywhere without a ridge.
+ *  - Nodes and points: by the cell rule of aos_gvd_clearance, node_site / node_region / node_d2 / node_ridge_d2 are
+ *    the values at the node's cell (AOS_SITE_NONE, AOS_REGION_NONE, AOS_D2_NONE, AOS_D2_NONE without a cell; every
+ *    node_ridge_d2 is AOS_D2_NONE when the ridge distance was not asked for). node_ridge_offset, metres:
+ *    (float)(sqrt((double)ridge_d2) * res), +inf for AOS_D2_NONE. A non-finite point has no cell.
+ * graph and grid = NULL are those of aos_gvd_clearance (the handle's last GVD graph; the skeleton that graph was
+ * built on), with AOS_E_STATE under the same conditions; labels must be NULL when grid is. opts = NULL is {0, 0}.
+ * AOS_E_INVALID: every case of aos_gvd_clearance, labels without a grid, min_component_cells > 1 with labels.
+ * width * height = 0: status 0, nothing launched, the counts 0 (n_components and n_regions -1 with labels), max_d2
+ * AOS_D2_NONE, the device pointers NULL, every node value NONE / +inf. Every call recomputes its fields; the outputs
+ * are library-owned and valid until the next aos_gvd_regions on the handle or aos_destroy. The call has buffers of
+ * its own: the field of an earlier aos_gvd_clearance stays valid across it.
+ * ------------------------------------------------------------------------------------------- */
+#define AOS_SITE_NONE 0xFFFFFFFFu
+#define AOS_REGION_NONE (-1)
+typedef struct aos_regions_opts {
+    int32_t min_component_cells;   /* <= 1: every component is kept                                            */
+    int32_t want_ridge_distance;   /* != 0: ridge_d2 is computed                                               */
+} aos_regions_opts;
+typedef struct aos_regions_out {
+    aos_grid_info info;
+    uint64_t n_occupied, n_sites, n_ridge;
+    int64_t n_components, n_regions;                 /* -1 with caller labels                                  */
+    uint32_t max_d2;                                 /* AOS_D2_NONE if n_sites == 0                            */
+    const uint32_t *site_device;                     /* width * height words each, on the handle's GPU         */
+    const int32_t *region_device;
+    const int8_t *ridge_device;
+    const uint32_t *ridge_d2_device;                 /* NULL unless opts.want_ridge_distance                   */
+    int32_t num_nodes;
+    const uint32_t *node_site;                       /* host, library-owned                                    */
+    const int32_t *node_region;
+    const uint32_t *node_d2, *node_ridge_d2;
+    const float *node_ridge_offset;                  /* metres                                                 */
+    float ms_label, ms_field, ms_ridge, ms_graph;    /* device time: sites and labels / the site field / region,
+                                                        ridge and ridge distance / the node sampling           */
+} aos_regions_out;
+int aos_gvd_regions(aos_ctx *ctx, const aos_path_graph *graph, const int8_t *grid, int grid_on_device,
+                    const aos_grid_info *info, const int32_t *labels, const aos_regions_opts *opts,
+                    aos_regions_out *out);
+/* A field of the last aos_gvd_regions copied to host memory. which: "site" (uint32), "region" (int32), "ridge" (int8),
+ * "ridge_d2" (uint32). AOS_E_STATE before any field exists; AOS_E_INVALID for an unknown name, a capacity_cells below
+ * width * height, a null dst behind cells, or "ridge_d2" when the last call did not compute it. */
+int aos_regions_field_copy(aos_ctx *ctx, const char *which, void *dst, uint64_t capacity_cells);
+/* The values of n points (x, y) against the last aos_gvd_regions' fields, by the node rule (e.g. /plan poses). Any
+ * output may be null. AOS_E_STATE before any field exists. */
+int aos_regions_points(aos_ctx *ctx, const double *xy, int32_t n, uint32_t *site, int32_t *region, uint32_t *d2,
+                       uint32_t *ridge_d2, float *ridge_offset_m);
+
 /* Diagnostics: copy an internal device grid of the last frame to host as int8 {0,100}.
  * which: "raster", "inflated", "opened", "skeleton_frameless". */
 int aos_debug_grid(aos_ctx *ctx, const char *which, int8_t *dst, uint64_t capacity);
