@@ -310,17 +310,18 @@ void Subdiv2D::swap_loop(int curr_edge, int first_point, int curr_point) {
 }
 
 // ---- the ring of an insert's star as arrays (subdiv2d.h) ----
-static constexpr int HO_PAD = 4;   // spare entries before slot 0 and after slot cap - 1 (one of each is the cyclic copy)
+static constexpr int HO_PAD = 4;   // spare entries before position 0 and after position cap - 1 (the cyclic copies)
 
-Subdiv2D::RingP Subdiv2D::ring_ptrs(Ring &r) {
-    return RingP{r.bd.data() + HO_PAD, r.bu.data() + HO_PAD, r.ba.data() + HO_PAD, r.sp.data() + HO_PAD,
-                 r.x.data() + HO_PAD,  r.y.data() + HO_PAD,  r.n.data() + HO_PAD,  r.ax.data() + HO_PAD,
-                 r.ay.data() + HO_PAD, r.an.data() + HO_PAD};
+Subdiv2D::RingP Subdiv2D::ring_ptrs(Ring &r) {   // indexed from the window's first slot
+    const size_t at = (size_t)HO_PAD + r.b;
+    return RingP{r.bd.data() + at, r.bu.data() + at, r.ba.data() + at, r.sp.data() + at, r.x.data() + at,
+                 r.y.data() + at,  r.n.data() + at,  r.ax.data() + at, r.ay.data() + at, r.an.data() + at};
 }
 
-void Subdiv2D::ring_reserve(Ring &r, int slots) {   // keeps the contents
-    if (slots <= r.cap) return;
-    const int cap = std::max(256, 2 * slots);
+void Subdiv2D::ring_reserve(Ring &r, int slots) {   // room for slots from the window's first on; keeps the contents
+    const int need = r.b + slots;
+    if (need <= r.cap) return;
+    const int cap = std::max(64, 2 * need);
     const size_t n = (size_t)cap + 2 * HO_PAD;
     r.bd.resize(n); r.bu.resize(n); r.ba.resize(n); r.sp.resize(n);
     r.x.resize(n); r.y.resize(n); r.n.resize(n); r.ax.resize(n); r.ay.resize(n); r.an.resize(n);
@@ -330,8 +331,9 @@ void Subdiv2D::ring_reserve(Ring &r, int slots) {   // keeps the contents
 // The one statement of what slot k of a ring around p owns in the records, and so of what is pending while its star
 // is deferred (subdiv2d.h): f(field, value) for Onext(L_k), the slot int of L_k (how the next insert finds its fan
 // triangle's slot), Oprev(Sym L_k+1), every field of the spoke S_k = x_k -> p and of Sym S_k, and firstEdge of x_k.
-// L = L_k, Ln = L_k+1, x = x_k, Sm / S / Sn = S_k-1 / S_k / S_k+1. R is the Rec array as ints (a directed edge e's
-// fields at R[2 e]: onext, oprev, origin, slot). The ring pass, retire() and for_pending() all go through it.
+// k is the slot's position in the buffer. L = L_k, Ln = L_k+1, x = x_k, Sm / S / Sn = S_k-1 / S_k / S_k+1. R is the
+// Rec array as ints (a directed edge e's fields at R[2 e]: onext, oprev, origin, slot). The ring pass, retire() and
+// for_pending() all go through it.
 template <class F>
 static inline void slot_fields(int *R, int *vfirst, int k, int L, int Ln, int x, int Sm, int S, int Sn, int p, F f) {
     const int sLn = Ln ^ 2, sS = S ^ 2;
@@ -347,16 +349,18 @@ static inline void slot_write(int *R, int *vfirst, int k, int L, int Ln, int x, 
     slot_fields(R, vfirst, k, L, Ln, x, Sm, S, Sn, p, [](int &field, int v) { field = v; });
 }
 
-// The ring pass: one pass over the boundary L_k (k in walk order; bd / sp padded cyclically at m) writes every slot's
-// fields. OpenCV's swapEdges' setEdgePoints(e, apex, p) and vtx[apex].firstEdge = e, and the rings of the final star,
-// are all in it. In a function of its own over plain restrict pointers the compiler keeps the loop's values (the
-// carried S_k-1, S_k, S_k+1) in registers.
+// The ring pass: one pass over the boundary L_k (k in walk order from the window's first slot, at position base;
+// bd / sp padded cyclically at m) writes every slot's fields. OpenCV's swapEdges' setEdgePoints(e, apex, p) and
+// vtx[apex].firstEdge = e, and the rings of the final star, are all in it. In a function of its own over plain
+// restrict pointers the compiler keeps the loop's values (the carried S_k-1, S_k, S_k+1) in registers (DESIGN.md 6.1,
+// round 5).
 __attribute__((noinline)) static void ring_pass(int *__restrict R, int *__restrict vfirst, const int *__restrict bd,
-                                                const int *__restrict bu, const int *__restrict sp, int m, int p) {
+                                                const int *__restrict bu, const int *__restrict sp, int m, int p,
+                                                int base) {
     int Sm = sp[m - 1], S = sp[0];
     for (int k = 0; k < m; ++k) {
         const int Sn = sp[k + 1];
-        slot_write(R, vfirst, k, bd[k], bd[k + 1], bu[k], Sm, S, Sn, p);
+        slot_write(R, vfirst, base + k, bd[k], bd[k + 1], bu[k], Sm, S, Sn, p);
         Sm = S; S = Sn;
     }
 }
@@ -383,7 +387,7 @@ __attribute__((noinline)) int Subdiv2D::cavity_walk(int e, const V2d &Pin, int s
     int *const stk = dfs_stack.data();
     int *top = stk;
     RingP n = ring_ptrs(N);
-    int cap = N.cap;
+    int cap = N.cap - N.b;
     const int hz = ho_hz;
     for (;;) {
         SDP_INC(dfs_steps);
@@ -401,7 +405,7 @@ __attribute__((noinline)) int Subdiv2D::cavity_walk(int e, const V2d &Pin, int s
             e = sym(onext(sym(e)));                            // w -> v
             continue;
         }
-        if (q >= cap) { ring_reserve(N, q + 1); n = ring_ptrs(N); cap = N.cap; }
+        if (q >= cap) { ring_reserve(N, q + 1); n = ring_ptrs(N); cap = N.cap - N.b; }
         n.bd[q] = e; n.bu[q] = o; n.ba[q] = w; n.sp[q] = O.spoke;
         n.x[q] = O.x; n.y[q] = O.y; n.n[q] = O.n2;
         n.ax[q] = T.x; n.ay[q] = T.y; n.an[q] = T.n2;
@@ -414,6 +418,7 @@ __attribute__((noinline)) int Subdiv2D::cavity_walk(int e, const V2d &Pin, int s
 }
 
 // ---- hand-over: the previous insert's star walked through its arrays (subdiv2d.h) ----
+AOS_AVX2 static int find_int(const int *a, int m, int v);
 #if defined(__x86_64__)
 #ifndef AOS_HO_VEC
 #define AOS_HO_VEC 1   // 0: every hand-over test and copy one slot at a time (the A/B of DESIGN.md 6.1)
@@ -422,8 +427,13 @@ __attribute__((noinline)) int Subdiv2D::cavity_walk(int e, const V2d &Pin, int s
 
 // Walk of the three roots when p lies in the fan triangle (x_k, x_k-1, c) of the previous star O (subdiv2d.h): the
 // roots are L_k (link), S_k-1 (descending chain) and Sym S_k (ascending chain); shift rotates the order
-// (ascending, descending, link) to the walk order eA, eB, e0. Writes the new ring into N; false: bail out.
-AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, int c, int sA, int &q_out) {
+// (ascending, descending, link) to the walk order eA, eB, e0. Writes the new ring into N; 0: bail out, 1: done.
+// INPLACE: the same tests, stamps and bail-outs in the same order, but nothing is stored into a ring but the leaves
+// of swapped links, which go into N as scratch (ho_plan says where). 2 (seam), 3 (swapped links) and 4 (no room) say
+// that ho_apply cannot build this ring in place: the caller takes a fresh stamp and runs the copying form, whose tests
+// up to that point repeat this walk's.
+template <bool INPLACE>
+AOS_AVX2 int Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, int c, int sA, int &q_out) {
     const RingP o = ring_ptrs(Oring);
     RingP n = ring_ptrs(N);
     const int m = Oring.m;
@@ -434,19 +444,22 @@ AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, i
     const HoV C4{_mm256_set1_pd(Cv.x), _mm256_set1_pd(Cv.y), _mm256_set1_pd(Cv.n2)};
     int q = 0, lf = -1;
     const int km1 = k ? k - 1 : m - 1;
+    if (INPLACE) { ho_plan.k = k; ho_plan.nsl = 0; }
 
-#define HO_ROOM(cnt) do { if (q + (cnt) > N.cap) { ring_reserve(N, q + (cnt)); n = ring_ptrs(N); } } while (0)
+#define HO_ROOM(cnt) do { if (N.b + q + (cnt) > N.cap) { ring_reserve(N, q + (cnt)); n = ring_ptrs(N); } } while (0)
 #define HO_XS(i) HoS{o.x[i], o.y[i], o.n[i]}
 #define HO_AS(i) HoS{o.ax[i], o.ay[i], o.an[i]}
 // a swap onto ring vertex v (the apex), whose spoke becomes s
-#define HO_SWAP(v, s) do { V2d &W_ = V[v]; if (W_.stamp == sA) return false; W_.stamp = sA; W_.spoke = (s); lf = (s); } while (0)
+#define HO_SWAP(v, s) do { V2d &W_ = V[v]; if (W_.stamp == sA) return 0; W_.stamp = sA; W_.spoke = (s); lf = (s); } while (0)
 // link slot j: a leaf is copied from the old ring (its right triangle is untouched), a swap leaves the star
 #define HO_LINK(j, swaps) do { \
         if (swaps) { \
+            if (INPLACE) { if (ho_plan.nsl == 2) return 3; ho_plan.sl[ho_plan.nsl] = HoLink{(j), q, 0}; } \
             q = cavity_walk(o.bd[j], Pv, sA, N, q, lf); \
-            if (q < 0) return false; \
+            if (q < 0) return 0; \
             lf = ho_lf; n = ring_ptrs(N); \
-        } else { \
+            if (INPLACE) { HoLink &l_ = ho_plan.sl[ho_plan.nsl++]; l_.cnt = q - l_.s0; } \
+        } else if (!INPLACE) { \
             HO_ROOM(1); \
             n.bd[q] = o.bd[j]; n.bu[q] = o.bu[j]; n.ba[q] = o.ba[j]; n.sp[q] = V[o.bu[j]].spoke; \
             n.x[q] = o.x[j]; n.y[q] = o.y[j]; n.n[q] = o.n[j]; n.ax[q] = o.ax[j]; n.ay[q] = o.ay[j]; n.an[q] = o.an[j]; \
@@ -454,6 +467,7 @@ AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, i
         } } while (0)
 // link slots j .. j + 3, all leaves: one copy per array (the spokes are the caller's)
 #define HO_COPY4(j) do { \
+        HO_ROOM(4); \
         _mm_storeu_si128((__m128i *)(n.bd + q), _mm_loadu_si128((const __m128i *)(o.bd + (j)))); \
         _mm_storeu_si128((__m128i *)(n.bu + q), _mm_loadu_si128((const __m128i *)(o.bu + (j)))); \
         _mm_storeu_si128((__m128i *)(n.ba + q), _mm_loadu_si128((const __m128i *)(o.ba + (j)))); \
@@ -496,10 +510,12 @@ AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, i
             }
             // the leaf S_j (apex x_j-1), then the stacked links L_j+1 .. L_k-1
             ho_jD = j;
-            HO_ROOM(1);
-            n.bd[q] = o.sp[j]; n.bu[q] = o.bu[j]; n.ba[q] = o.bu[j - 1]; n.sp[q] = V[o.bu[j]].spoke;
-            n.x[q] = o.x[j]; n.y[q] = o.y[j]; n.n[q] = o.n[j]; n.ax[q] = o.x[j - 1]; n.ay[q] = o.y[j - 1]; n.an[q] = o.n[j - 1];
-            ++q;
+            if (!INPLACE) {
+                HO_ROOM(1);
+                n.bd[q] = o.sp[j]; n.bu[q] = o.bu[j]; n.ba[q] = o.bu[j - 1]; n.sp[q] = V[o.bu[j]].spoke;
+                n.x[q] = o.x[j]; n.y[q] = o.y[j]; n.n[q] = o.n[j]; n.ax[q] = o.x[j - 1]; n.ay[q] = o.y[j - 1]; n.an[q] = o.n[j - 1];
+                ++q;
+            }
             int i = j + 1 == m ? 0 : j + 1;
             for (int cnt = nsw; cnt > 0;) {
                 if (AOS_HO_VEC && cnt >= 4 && i + 4 <= m) {
@@ -508,10 +524,11 @@ AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, i
                     g_sdprof.dfs_steps += 4;
 #endif
                     if (mask == 0) {
-                        HO_ROOM(4);
-                        HO_COPY4(i);
-                        _mm_storeu_si128((__m128i *)(n.sp + q), _mm_loadu_si128((const __m128i *)(o.sp + i + 1)));   // x_i took S_i+1
-                        q += 4;
+                        if (!INPLACE) {
+                            HO_COPY4(i);
+                            _mm_storeu_si128((__m128i *)(n.sp + q), _mm_loadu_si128((const __m128i *)(o.sp + i + 1)));   // x_i took S_i+1
+                            q += 4;
+                        }
                     } else {
                         for (int l = 0; l < 4; ++l) HO_LINK(i + l, (mask >> l) & 1);
                     }
@@ -524,7 +541,7 @@ AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, i
                     i = i + 1 == m ? 0 : i + 1; --cnt;
                 }
             }
-            if (nsw) n.sp[q - 1] = V[o.bu[km1]].spoke;   // the last link's origin x_k-1 is a root
+            if (!INPLACE && nsw) n.sp[q - 1] = V[o.bu[km1]].spoke;   // the last link's origin x_k-1 is a root
         } else {
             // Sym S_j = c -> x_j for j = k, k + 1, ...: T = x_j+1, O = c, D = x_j; a swap walks L_j+1 at once, then Sym S_j+1
             int j = k;
@@ -538,11 +555,12 @@ AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, i
 #endif
                     if (smask == 0xf && lmask == 0) {
                         for (int i = 0; i < 4; ++i) HO_SWAP(o.bu[j + 1 + i], o.sp[j + i] ^ 2);
-                        HO_ROOM(4);
-                        HO_COPY4(j + 1);
-                        _mm_storeu_si128((__m128i *)(n.sp + q),
-                                         _mm_xor_si128(_mm_loadu_si128((const __m128i *)(o.sp + j)), _mm_set1_epi32(2)));   // x_j+1 took Sym S_j
-                        q += 4;
+                        if (!INPLACE) {
+                            HO_COPY4(j + 1);
+                            _mm_storeu_si128((__m128i *)(n.sp + q),
+                                             _mm_xor_si128(_mm_loadu_si128((const __m128i *)(o.sp + j)), _mm_set1_epi32(2)));   // x_j+1 took Sym S_j
+                            q += 4;
+                        }
                         j += 4;
                         continue;
                     }
@@ -566,10 +584,12 @@ AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, i
             }
             // the leaf Sym S_j (apex x_j+1)
             ho_jA = j;
-            HO_ROOM(1);
-            n.bd[q] = o.sp[j] ^ 2; n.bu[q] = c; n.ba[q] = o.bu[j + 1]; n.sp[q] = Cv.spoke;
-            n.x[q] = Cv.x; n.y[q] = Cv.y; n.n[q] = Cv.n2; n.ax[q] = o.x[j + 1]; n.ay[q] = o.y[j + 1]; n.an[q] = o.n[j + 1];
-            ++q;
+            if (!INPLACE) {
+                HO_ROOM(1);
+                n.bd[q] = o.sp[j] ^ 2; n.bu[q] = c; n.ba[q] = o.bu[j + 1]; n.sp[q] = Cv.spoke;
+                n.x[q] = Cv.x; n.y[q] = Cv.y; n.n[q] = Cv.n2; n.ax[q] = o.x[j + 1]; n.ay[q] = o.y[j + 1]; n.an[q] = o.n[j + 1];
+                ++q;
+            }
         }
     }
 #undef HO_ROOM
@@ -580,7 +600,116 @@ AOS_AVX2 bool Subdiv2D::ho_fast(Ring &Oring, Ring &N, int k, int shift, int p, i
 #undef HO_COPY4
     ho_lf = lf;
     q_out = q;
-    return true;
+    if (INPLACE) {
+        // a chain that crossed the seam: its end unwrapped, below the window's first slot or above its last. The kept
+        // run is then jD + 1 .. jA; a swapped link goes to the end it lies at most one slot from (sl[0] low, sl[1] high)
+        HoPlan &pl = ho_plan;
+        int jD = ho_jD, jA = ho_jA, wrap = 0;
+        if (jD >= k) { jD -= m; wrap = -1; }
+        if (jA < k) { if (wrap) return 2; jA += m; wrap = 1; }
+        if (wrap && !seam_copy) return 2;
+        for (int i = 0; i < pl.nsl; ++i) {
+            if (wrap < 0 && pl.sl[i].j > ho_jD) pl.sl[i].j -= m;
+            if (wrap > 0 && pl.sl[i].j <= ho_jA) pl.sl[i].j += m;
+        }
+        pl.jD = jD; pl.jA = jA; pl.wrap = wrap;
+        pl.lo = pl.hi = false;
+        if (pl.nsl == 2) {
+            if (pl.sl[0].j > pl.sl[1].j) std::swap(pl.sl[0], pl.sl[1]);
+            if (pl.sl[0].j - (jD + 1) > 1 || jA - pl.sl[1].j > 1) return 3;
+            pl.lo = pl.hi = true;
+        } else if (pl.nsl == 1) {
+            if (pl.sl[0].j - (jD + 1) <= 1) pl.lo = true;
+            else if (jA - pl.sl[0].j <= 1) { pl.hi = true; pl.sl[1] = pl.sl[0]; }
+            else return 3;
+        }
+        const int first = jD - (pl.lo ? pl.sl[0].cnt - 1 : 0) - (wrap < 0), end = jA + 2 + (pl.hi ? pl.sl[1].cnt - 1 : 0);
+        if (Oring.b + first < 0 || Oring.b + end > Oring.cap) return 4;   // no room: the copying walk re-bases
+    }
+    return 1;
+}
+
+// The new ring of an in-place insert, built in the old ring's window after retire() has read it (subdiv2d.h): O is the
+// old ring, S the scratch buffer with the swapped links' leaves, ho_plan / ho_jD / ho_jA what ho_fast<true> found.
+// Leaves the position (relative to the new window) and kind of recentEdge = e0 in s_out / kind_out.
+AOS_AVX2 void Subdiv2D::ho_apply(Ring &Oring, Ring &Sring, int shift, int e0, int c, int &s_out, int &kind_out) {
+    const RingP o = ring_ptrs(Oring), sc = ring_ptrs(Sring);
+    const HoPlan &pl = ho_plan;
+    const V2d *const V = vd.data();
+    const int k = pl.k, jD = pl.jD, jA = pl.jA;
+    const int dlo = pl.lo ? pl.sl[0].cnt - 1 : 0, dhi = pl.hi ? pl.sl[1].cnt - 1 : 0;
+    const bool mlo = pl.lo && pl.sl[0].j == jD + 2, mhi = pl.hi && pl.sl[1].j == jA - 1;   // L_jD+1 / L_jA moves
+    auto put = [&](int d, int bd, int bu, int ba, int sp, double x, double y, double n, double ax, double ay, double an) {
+        o.bd[d] = bd; o.bu[d] = bu; o.ba[d] = ba; o.sp[d] = sp;
+        o.x[d] = x; o.y[d] = y; o.n[d] = n; o.ax[d] = ax; o.ay[d] = ay; o.an[d] = an;
+    };
+    auto move = [&](const RingP &f, int from, int d) {
+        put(d, f.bd[from], f.bu[from], f.ba[from], f.sp[from], f.x[from], f.y[from], f.n[from], f.ax[from], f.ay[from], f.an[from]);
+    };
+    if (pl.wrap) {   // the slots beyond the seam (and the one whose vertex is the end leaf's apex) to the other end
+        const int m = Oring.m;
+        if (pl.wrap < 0) for (int i = ho_jD - 1; i < m; ++i) move(o, i, i - m);
+        else for (int i = 0; i <= ho_jA + 1; ++i) move(o, i, i + m);
+#ifdef AOS_SD_PROF
+        g_sdprof.ho_slots_written += pl.wrap < 0 ? m - ho_jD + 1 : ho_jA + 2;
+        ++g_sdprof.ip_unwrapped;
+#endif
+        ++n_ip_unwrap;
+    }
+    // the old values the two end leaves are made of, before anything is written
+    const int spD = o.sp[jD], spA = o.sp[jA], uD = o.bu[jD], aD = o.bu[jD - 1], aA = o.bu[jA + 1];
+    const double xD = o.x[jD], yD = o.y[jD], nD = o.n[jD], axD = o.x[jD - 1], ayD = o.y[jD - 1], anD = o.n[jD - 1];
+    const double axA = o.x[jA + 1], ayA = o.y[jA + 1], anA = o.n[jA + 1];
+    // sp over the kept run and slot jD: x_i took S_i+1 for i < k - 1 (ascending copy), Sym S_i-1 for i > k (descending
+    // copy: the source overlaps the destination from below); x_k-1 and x_k are roots
+    {
+        int i = jD;
+        for (; i + 8 <= k - 1; i += 8)
+            _mm256_storeu_si256((__m256i *)(o.sp + i), _mm256_loadu_si256((const __m256i *)(o.sp + i + 1)));
+        for (; i < k - 1; ++i) o.sp[i] = o.sp[i + 1];
+        const __m256i two = _mm256_set1_epi32(2);
+        for (i = jA; i - 7 >= k + 1; i -= 8)
+            _mm256_storeu_si256((__m256i *)(o.sp + i - 7), _mm256_xor_si256(_mm256_loadu_si256((const __m256i *)(o.sp + i - 8)), two));
+        for (; i >= k + 1; --i) o.sp[i] = o.sp[i - 1] ^ 2;
+    }
+    o.sp[k - 1] = V[o.bu[k - 1]].spoke;
+    o.sp[k] = V[o.bu[k]].spoke;
+    // the low end, in ascending positions: the leaf S_jD, the moved L_jD+1, the swapped link's leaves
+    const int pD = jD - dlo;
+    put(pD, spD, uD, aD, o.sp[jD], xD, yD, nD, axD, ayD, anD);
+    if (mlo) move(o, jD + 1, jD + 1 - dlo);
+    if (pl.lo)
+        for (int i = 0, d = pl.sl[0].j - dlo; i < pl.sl[0].cnt; ++i) move(sc, pl.sl[0].s0 + i, d + i);
+    // the high end, in descending positions: the leaf Sym S_jA, the moved L_jA, the swapped link's leaves
+    const int pA = jA + 1 + dhi;
+    const V2d &Cv = V[c];
+    put(pA, spA ^ 2, c, aA, Cv.spoke, Cv.x, Cv.y, Cv.n2, axA, ayA, anA);
+    if (mhi) move(o, jA, jA + dhi);
+    if (pl.hi)
+        for (int i = pl.sl[1].cnt - 1, d = pl.sl[1].j; i >= 0; --i) move(sc, pl.sl[1].s0 + i, d + i);
+#ifdef AOS_SD_PROF
+    g_sdprof.ho_slots_written += 2 + mlo + mhi + (pl.lo ? pl.sl[0].cnt : 0) + (pl.hi ? pl.sl[1].cnt : 0);
+#endif
+    // recentEdge = e0: a leaf (L_k, or a chain's root that did not swap), else the spoke of the vertex that took it
+    int s, kind = 0;
+    if (shift == 0) s = k == jD + 1 && mlo ? k - dlo : k == jA && mhi ? k + dhi : k;
+    else if (shift == 2) {   // e0 = S_k-1: taken by x_k-2
+        if (jD == k - 1) s = pD;
+        else { kind = 2; s = k - 2 == jD ? pD : k - 2 == jD + 1 && mlo ? k - 2 - dlo : k - 2; }
+    } else {                 // e0 = Sym S_k: taken by x_k+1
+        if (jA == k) s = pA;
+        else { kind = 2; s = k + 1 == jA && mhi ? k + 1 + dhi : pl.hi && pl.sl[1].j == k + 1 ? k + dhi + 1 : k + 1; }
+    }
+    if ((kind == 0 ? o.bd[s] : o.sp[s]) != e0) {   // (L_k swapped: the spoke of its apex, among its leaves)
+        const int m = pA + 1 - pD;
+        s = find_int(o.bd + pD, m, e0);
+        if (s >= 0) kind = 0; else { kind = 2; s = find_int(o.sp + pD, m, e0); }
+        s = s >= 0 ? s + pD : INT_MIN;
+    }
+    s_out = s == INT_MIN ? -1 : s - pD;
+    kind_out = kind;
+    Oring.b += pD;
+    Oring.m = pA + 1 - pD;
 }
 #endif   // __x86_64__
 
@@ -600,7 +729,8 @@ AOS_AVX2 static int find_int(const int *a, int m, int v) {   // the first i < m 
 // Cavity form of an INSIDE insert (subdiv2d.h). e0 = locate's edge: p lies left of it, inside the triangle (e0,
 // Lnext e0, Lnext^2 e0). The walk starts either through the previous star's arrays (ho_fast, with the hand-over on)
 // or, when p does not lie in a fan triangle of the previous insert, from the three roots by cavity_walk; both leave
-// the new star's ring in the other buffer. Returns false, with nothing of the new star in the records, when the walk meets an apex that
+// the new star's ring in the other buffer, but for a hand-over insert that can build it in the old ring's window
+// (ho_fast<true> and ho_apply, subdiv2d.h). Returns false, with nothing of the new star in the records, when the walk meets an apex that
 // is already a cavity vertex; the caller then runs the connects and the swap loop.
 bool Subdiv2D::insert_cavity(int e0, int p) {
     if (++stamp >= (1 << 29)) {
@@ -608,14 +738,14 @@ bool Subdiv2D::insert_cavity(int e0, int p) {
         for (V2d &x : vd) x.stamp = 0;
         stamp = 1; ho_stamp = -1;
     }
-    const int sA = 2 * stamp;
+    int sA = 2 * stamp;
     Ring &O = ho[ho_cur], &N = ho[ho_cur ^ 1];
     int eA = 0, eB = 0, first, v1, v2;
     int shift = -1, k = -1;
     if (loc_k >= 0) {
         // located on the ring arrays (locate_star): slot, rotation and corners without a record read
         const RingP o = ring_ptrs(O);
-        k = loc_k; shift = loc_shift;
+        k = loc_k - O.b; shift = loc_shift;
         const int xk = o.bu[k], xk1 = o.bu[k - 1], c = ho_c;
         if (shift == 0) { first = xk; v1 = xk1; v2 = c; }         // e0 = L_k
         else if (shift == 2) { first = xk1; v1 = c; v2 = xk; }    // e0 = S_k-1
@@ -641,8 +771,10 @@ bool Subdiv2D::insert_cavity(int e0, int p) {
     F.stamp = A.stamp = B.stamp = sA;
     F.spoke = cn[0]; A.spoke = cn[1]; B.spoke = cn[2];           // first -> p, v1 -> p, v2 -> p
     const V2d P = vd[p];
+    N.b = ring_slack;   // (a walk into the other buffer puts the window back at the slack)
     ring_reserve(N, 8);
     int q = 0, lf = -1;
+    bool inplace = false;
     SDP_T0(t_dfs);
     bool fast = loc_k >= 0;
     if (!fast && ho_valid) {
@@ -654,7 +786,7 @@ bool Subdiv2D::insert_cavity(int e0, int p) {
         else if (v1 == c) { shift = 2; L = eA; asc = eB; desc = e0; }
         else if (first == c) { shift = 1; desc = eA; L = eB; asc = e0; }
         if (shift >= 0) {
-            k = chk(ri()[2 * (ptrdiff_t)L + 3]);
+            k = (int)((unsigned)chk(ri()[2 * (ptrdiff_t)L + 3]) - (unsigned)O.b);
             const RingP o = ring_ptrs(O);
             fast = (unsigned)k < (unsigned)O.m && o.bd[k] == L && (o.sp[k] ^ 2) == asc && o.sp[k - 1] == desc;
         }
@@ -664,7 +796,27 @@ bool Subdiv2D::insert_cavity(int e0, int p) {
         last_ho_slot = k; last_ho_ring = O.m;
         ho_hz = pending ? ho_stamp : -1;
         ho_pocket = false;
-        if (!ho_fast(O, N, k, shift, p, ho_c, sA, q)) {
+        int res = 1;
+        if (use_inpl) {
+            res = ho_fast<true>(O, N, k, shift, p, ho_c, sA, q);
+            inplace = res == 1;
+            if (res == 0) SDP_INC(ip_bail);
+            if (res >= 2) {
+                ++n_ip_fallback;
+                n_rebase += res == 4;
+                n_ip_seam += res == 2;
+#ifdef AOS_SD_PROF
+                ++(res == 2 ? g_sdprof.ip_seam : res == 3 ? g_sdprof.ip_interior : g_sdprof.ip_rebase);
+#endif
+                // a fresh stamp: the copying walk repeats the tests, and finds the stamps of this attempt older than
+                // its own as it would have found the ones before them
+                ++stamp;
+                sA = 2 * stamp;
+                F.stamp = A.stamp = B.stamp = sA;
+            }
+        }
+        if (res >= 1 && !inplace) res = ho_fast<false>(O, N, k, shift, p, ho_c, sA, q);
+        if (res == 0) {
             if (ho_pocket) ++n_ho_pocket; else ++n_ho_bail;
             flush();   // (ho_fast has changed no record: the pending ring is still the whole truth)
             ho_valid = false; last_ho_slot = -1;
@@ -685,12 +837,6 @@ bool Subdiv2D::insert_cavity(int e0, int p) {
     }
     SDP_ADD(t_dfs, t_dfs);
     SDP_T0(t_wr);
-    const int m = q;
-    const RingP n = ring_ptrs(N);   // (cap >= m, and HO_PAD spare entries follow)
-    N.m = m;
-    n.bd[m] = n.bd[0]; n.bu[m] = n.bu[0]; n.sp[m] = n.sp[0]; n.x[m] = n.x[0]; n.y[m] = n.y[0]; n.n[m] = n.n[0];
-    n.bd[-1] = n.bd[m - 1]; n.bu[-1] = n.bu[m - 1]; n.sp[-1] = n.sp[m - 1];
-    n.x[-1] = n.x[m - 1]; n.y[-1] = n.y[m - 1]; n.n[-1] = n.n[m - 1];
     // The outcome. OpenCV's two connectEdges (after the first newEdge + splice) number the three new quad-edges
     // first -> p, v1 -> p, v2 -> p in that order; everything else they write (the rings of first, v1, v2 and p next to
     // the new edges, their end points, firstEdge) is rewritten by the ring pass, which sets every field of every spoke
@@ -698,16 +844,38 @@ bool Subdiv2D::insert_cavity(int e0, int p) {
     const int c0 = new_edge(), c1 = new_edge(), c2 = new_edge();   // (= cn[0 .. 2])
     (void)c0; (void)c1;
     vfirst[p] = sym(lf >= 0 ? lf : c2);   // the last setEdgePoints with p as destination
-    if (pending) retire(O, ho_jA, ho_jD);   // (fast: what survives of the old star; the rest is N's to write)
-    ho_cur ^= 1; ho_c = p; ho_valid = use_ho; ho_stamp = sA;
+    if (pending) retire(O, ho_jA, ho_jD);   // (fast: what survives of the old star; the rest is the new ring's to write)
+    // only now, with the old ring read for the last time, may an in-place insert write into its window
+    int rs = -1, rkind = 0;
+#if defined(__x86_64__)
+    if (inplace) { ho_apply(O, N, shift, e0, ho_c, rs, rkind); ++n_inplace; SDP_INC(ip_done); }
+    else
+#endif
+    {
+        N.m = q;
+        ho_cur ^= 1;
+#ifdef AOS_SD_PROF
+        if (fast) g_sdprof.ho_slots_written += q;
+#endif
+    }
+    Ring &Rn = ho[ho_cur];
+    const int m = Rn.m;
+    const RingP n = ring_ptrs(Rn);   // (the cyclic copies at the window's ends: HO_PAD spare entries lie outside the buffer's slots)
+    n.bd[m] = n.bd[0]; n.bu[m] = n.bu[0]; n.sp[m] = n.sp[0]; n.x[m] = n.x[0]; n.y[m] = n.y[0]; n.n[m] = n.n[0];
+    n.bd[-1] = n.bd[m - 1]; n.bu[-1] = n.bu[m - 1]; n.sp[-1] = n.sp[m - 1];
+    n.x[-1] = n.x[m - 1]; n.y[-1] = n.y[m - 1]; n.n[-1] = n.n[m - 1];
+    ho_c = p; ho_valid = use_ho; ho_stamp = sA;
     n_handover += fast;
     pending = false;
     if (use_ho & use_def) {   // (a star is left pending only where the next insert can walk it)
         // recentEdge = e0 in the new ring: the last leaf if its test did not swap, else the spoke of its apex
-        int s = m - 1, kind = 0;
-        if (n.bd[s] != e0) { kind = 2; s = find_int(n.sp, m, e0); }
+        int s = rs, kind = rkind;
+        if (!inplace) {
+            s = m - 1; kind = 0;
+            if (n.bd[s] != e0) { kind = 2; s = find_int(n.sp, m, e0); }
+        }
         if (s >= 0) {
-            pending = true; rs_kind = kind; rs_slot = s;
+            pending = true; rs_kind = kind; rs_slot = Rn.b + s;
             ++n_deferred;
 #ifdef AOS_SD_POISON
             for_pending([](int &f) { f = INT_MIN; });
@@ -716,7 +884,7 @@ bool Subdiv2D::insert_cavity(int e0, int p) {
     }
     static_assert(sizeof(Rec) == 32 && sizeof(Half) == 16 && offsetof(Half, op) == 4 && offsetof(Half, org) == 8 &&
                   offsetof(Half, x) == 12, "slot_fields: Rec layout");
-    if (!pending) ring_pass(ri(), vfirst.data(), n.bd, n.bu, n.sp, m, p);
+    if (!pending) ring_pass(ri(), vfirst.data(), n.bd, n.bu, n.sp, m, p, Rn.b);
     SDP_ADD(t_write, t_wr);
     return true;
 }
@@ -727,7 +895,7 @@ void Subdiv2D::flush() {
     SDP_T0(t_wr);
     Ring &R = ho[ho_cur];
     const RingP r = ring_ptrs(R);
-    ring_pass(ri(), vfirst.data(), r.bd, r.bu, r.sp, R.m, ho_c);
+    ring_pass(ri(), vfirst.data(), r.bd, r.bu, r.sp, R.m, ho_c, R.b);
     pending = false;
     SDP_ADD(t_write, t_wr);
 }
@@ -745,7 +913,7 @@ void Subdiv2D::retire(Ring &O, int jA, int jD) {
     g_sdprof.kept_slots += (jD - jA + m) % m + 1;
 #endif
     for (int j = jA;; j = j + 1 == m ? 0 : j + 1) {
-        slot_write(R, vfirst.data(), j, o.bd[j], o.bd[j + 1], o.bu[j], o.sp[j - 1], o.sp[j], o.sp[j + 1], c);
+        slot_write(R, vfirst.data(), O.b + j, o.bd[j], o.bd[j + 1], o.bu[j], o.sp[j - 1], o.sp[j], o.sp[j + 1], c);
         if (j == jD) break;
     }
 }
@@ -755,7 +923,7 @@ template <class Fn> void Subdiv2D::for_pending(Fn f) {
     Ring &Rg = ho[ho_cur];
     const RingP r = ring_ptrs(Rg);
     for (int k = 0; k < Rg.m; ++k)
-        slot_fields(ri(), vfirst.data(), k, r.bd[k], r.bd[k + 1], r.bu[k], r.sp[k - 1], r.sp[k], r.sp[k + 1], ho_c,
+        slot_fields(ri(), vfirst.data(), Rg.b + k, r.bd[k], r.bd[k + 1], r.bu[k], r.sp[k - 1], r.sp[k], r.sp[k + 1], ho_c,
                     [&](int &field, int) { f(field); });
 }
 
@@ -774,7 +942,7 @@ bool Subdiv2D::locate_star(float px, float py, int &out_edge) {
         const double cw = (dx - x) * (oy - y) - (dy - y) * (ox - x);
         return (cw > 0) - (cw < 0);
     };
-    int kind = rs_kind, s = rs_slot;
+    int kind = rs_kind, s = rs_slot - Rg.b;
     SDP_INC(star_loc);
     double ox = r.x[s], oy = r.y[s], dx, dy;
     if (kind == 0) { dx = r.x[s - 1]; dy = r.y[s - 1]; } else { dx = C.x; dy = C.y; }
@@ -820,6 +988,7 @@ bool Subdiv2D::locate_star(float px, float py, int &out_edge) {
         if (kind == 0) { recent = r.bd[s]; loc_k = s; loc_shift = 0; }
         else if (kind == 2) { recent = r.sp[s]; loc_k = s + 1 == m ? 0 : s + 1; loc_shift = 2; }
         else { recent = r.sp[s] ^ 2; loc_k = s; loc_shift = 1; }
+        loc_k += Rg.b;
         out_edge = recent;
         SDP_INC(star_found);
     }

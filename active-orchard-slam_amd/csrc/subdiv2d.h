@@ -66,6 +66,24 @@
 //     that is not in the cavity yet (a pocket of a non-convex star): its child edge can be Sym L_i, whose Oprev is
 //     pending. Ring vertices carry O's stamp, so the swap sees it for free: flush, swap loop (n_ho_pocket).
 //   * flush() runs the pass on the pending ring. Everything that reads records generically calls it first.
+//
+// The ring as a window, and the in-place hand-over (set_inplace, on by default with the hand-over). A ring lives in a
+// linear buffer as a window [b, b + m) with slack on both sides, cyclic from its last slot to its first; the cyclic pad
+// entries sit at the window's ends. Slot positions are absolute buffer positions: the slot int of a link edge, rs_slot
+// and loc_k are positions (the code indexes the window from its first slot). The new ring of a hand-over insert is the
+// old ring's run of link slots jD + 1 .. jA carried over unchanged, between two new leaves: S_jD in position jD (same
+// origin, new edge and apex) and Sym S_jA in position jA + 1. Where the fan triangle is known and every swapped link
+// lies at most one slot from an end of the run, the insert runs in place: ho_fast<true> makes the same tests in the same order with the same stamps but stores nothing into a
+// ring (a swapped link's leaves go into the other buffer as scratch), retire() reads the old ring, and only then
+// ho_apply() trims the window, shifts sp toward k from both sides (x_i took S_i+1 below k, Sym S_i-1 above it; the
+// roots' spokes come from the vertices), writes the two end leaves and moves the leaves of an end-adjacent swapped
+// link (and the one carried slot outside it) into place. The seam normally lies in the dropped range jA + 1 .. jD - 1
+// (it is where the centre before last sits in the ring); where one chain has crossed it, ho_apply first copies the
+// slots beyond the seam to the window's other end, which makes the run contiguous again. Any other outcome (both
+// chains across the seam, a swapped link further in, three or more swapped links, no room left in the buffer) takes a
+// fresh stamp and runs the copying
+// walk into the other buffer, which puts the window back at the slack (that copy is the re-base). A walk that bails
+// out has changed neither a record nor a ring in either form.
 // -DAOS_SD_POISON (checkers only) stores INT_MIN in every field as it becomes pending and counts record reads that
 // return it (sd_poison_reads): a stale read fails deterministically.
 #pragma once
@@ -76,6 +94,7 @@
 
 #define AOS_SD_HANDOVER 1   // set_handover(), n_handover and n_ho_bail exist (tools/sdcheck/sdprof.cpp)
 #define AOS_SD_DEFERRED 1   // set_deferred(), flush(), n_deferred and n_ho_pocket exist
+#define AOS_SD_INPLACE 1    // set_inplace(), n_inplace, n_ip_fallback and n_rebase exist
 
 namespace aos {
 
@@ -85,6 +104,10 @@ struct SdProf {
     // deferred star: locates started on the ring arrays, those that ended there, their steps; slots of the rings that
     // were retired and how many of them kept their spoke
     unsigned long long star_loc = 0, star_found = 0, star_steps = 0, ring_slots = 0, kept_slots = 0;
+    // in-place hand-over: inserts done in place, and those of them with a chain across the seam; attempts redone by the copying walk because the seam lay in the kept
+    // run, because of a swapped link further in than one slot from an end (or a third one), and for want of room (the
+    // re-bases); attempts that bailed out (swap loop); ring slots written by hand-over inserts of either form
+    unsigned long long ip_done = 0, ip_unwrapped = 0, ip_seam = 0, ip_interior = 0, ip_rebase = 0, ip_bail = 0, ho_slots_written = 0;
 };
 extern SdProf g_sdprof;
 #ifdef AOS_SD_POISON
@@ -106,6 +129,15 @@ class Subdiv2D {
     // leave a cavity insert's star pending in the ring arrays (see above; only with the hand-over on); off: every
     // insert runs its ring pass
     void set_deferred(bool on) { flush(); use_def = on; }
+    // build a hand-over insert's ring in the previous ring's window where that is possible (see above); off: every
+    // hand-over insert copies into the other buffer
+    void set_inplace(bool on) { flush(); use_inpl = on; }
+    // test hook: slots of slack the copying walk leaves below a new window (and at least as many above); small values
+    // force re-bases
+    void set_ring_slack(int slots) { flush(); ho_valid = false; ring_slack = slots < 1 ? 1 : slots; }
+    // test hook: off: an insert with a chain across the window's seam is redone by the copying walk and not built in
+    // place from copied ends
+    void set_seam_copy(bool on) { seam_copy = on; }
     void flush();                    // writes a pending star into the records (no-op without one)
     bool star_pending() const { return pending; }
     static bool simd_ok() {
@@ -122,6 +154,11 @@ class Subdiv2D {
     long n_ho_bail = 0;              // hand-over walks that met a cavity vertex twice: redone by the swap loop
     long n_deferred = 0;             // inserts that left their star pending (part of n_cavity)
     long n_ho_pocket = 0;            // hand-over walks whose swap had a ring vertex of the pending star as apex: flushed, swap loop
+    long n_inplace = 0;              // hand-over inserts that built their ring in place (part of n_handover)
+    long n_ip_fallback = 0;          // in-place attempts redone by the copying walk (seam, interior swapped link, re-base)
+    long n_rebase = 0;               // of those, the ones that only lacked room in the buffer
+    long n_ip_seam = 0;              // and the ones with the window's seam inside the kept run
+    long n_ip_unwrap = 0;            // in-place inserts that copied the slots beyond the seam to the window's other end
     int last_ho_slot = -1, last_ho_ring = 0;   // the last insert's fan-triangle slot and ring length (-1: no hand-over)
     // getVoronoiFacetList(idx = {}): per real vertex (in vertex order) the facet polygon.
     // Emits the reference's edge list directly: (p_i, p_{i+1 mod n}) for facets with >= 2 points
@@ -169,16 +206,24 @@ class Subdiv2D {
     struct Ring {
         std::vector<int> bd, bu, ba, sp;
         std::vector<double> x, y, n, ax, ay, an;
-        int cap = 0, m = 0;
+        int cap = 0, m = 0, b = 0;   // slots in the buffer; the window [b, b + m)
     };
-    struct RingP { int *bd, *bu, *ba, *sp; double *x, *y, *n, *ax, *ay, *an; };   // slot 0 of each array
+    struct RingP { int *bd, *bu, *ba, *sp; double *x, *y, *n, *ax, *ay, *an; };   // the window's first slot in each array
     Ring ho[2];
     int ho_cur = 0, ho_c = 0, ho_lf = -1;
-    bool ho_valid = false, use_ho = simd_ok();
+    bool ho_valid = false, use_ho = simd_ok(), use_inpl = true;
+    int ring_slack = 256;
+    bool seam_copy = true;
+    // what ho_fast<true> found, for ho_apply: the fan triangle's slot, the chain ends and up to two swapped links (slot,
+    // first scratch slot in the other buffer, leaves), all relative to the window and unwrapped: where a chain crossed
+    // the seam, wrap says which end of the window the slots beyond it are copied to (-1: the top ones below the first
+    // slot, 1: the bottom ones above the last), and jD < 0 or jA >= m
+    struct HoLink { int j, s0, cnt; };
+    struct HoPlan { int k = 0, nsl = 0, jD = 0, jA = 0, wrap = 0; bool lo = false, hi = false; HoLink sl[2]; } ho_plan;   // sl[0]: low end, sl[1]: high end
     // deferred star: ho[ho_cur] is pending; recentEdge as (kind, slot) of that ring; the fan triangle locate_star found
     bool pending = false, use_def = true, ho_pocket = false;
-    int rs_kind = 0, rs_slot = 0;    // kind: 0 L_s, 2 S_s, 3 Sym S_s
-    int loc_k = -1, loc_shift = 0;   // set by locate_star (loc_k < 0: the generic locate ran)
+    int rs_kind = 0, rs_slot = 0;    // kind: 0 L_s, 2 S_s, 3 Sym S_s; rs_slot: a position
+    int loc_k = -1, loc_shift = 0;   // set by locate_star: the fan triangle's position (loc_k < 0: the generic locate ran)
     int ho_stamp = -1, ho_hz = -1;   // the pending ring's vertex stamp; the stamp cavity_walk treats as a pocket (-1: none)
     int ho_jA = 0, ho_jD = 0;        // ho_fast: the slots where the ascending and descending chains ended
     float tlx = 0, tly = 0, brx = 0, bry = 0;
@@ -224,7 +269,9 @@ class Subdiv2D {
     static void ring_reserve(Ring &r, int slots);
     bool insert_cavity(int e0, int curr_point);
     int cavity_walk(int e, const V2d &P, int sA, Ring &N, int q, int last_flip);
-    bool ho_fast(Ring &O, Ring &N, int k, int shift, int p, int c, int sA, int &q_out);   // (x86-64 only)
+    // (x86-64 only) 0: bailed out, 1: done; 2 / 3 / 4: not possible in place (seam / swapped links / no room)
+    template <bool INPLACE> int ho_fast(Ring &O, Ring &N, int k, int shift, int p, int c, int sA, int &q_out);
+    void ho_apply(Ring &O, Ring &S, int shift, int e0, int c, int &s_out, int &kind_out);
     void calc_voronoi();   // calcVoronoi on the exported layout (qx), creating the virtual vertices
     int facet_next(int e) const;
 };

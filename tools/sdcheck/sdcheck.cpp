@@ -5,6 +5,8 @@
 // insert (same_state looks through a flushed view and leaves the star pending), and compared only after the last
 // insert, so that pending stars follow each other with no call in between. Built with -DAOS_SD_POISON, every pending
 // field holds INT_MIN and a record read that returns it fails the case.
+// The in-place leg (a hand-over insert builds its ring in the previous ring's window, subdiv2d.h) runs in the same two
+// forms; the other legs run with it off, so the copying walk stays the reference it is compared with.
 // usage: sdcheck [seeds.bin]   (seeds.bin: int n, n double pairs, 4 double bounds)
 #include "subdiv2d.h"
 
@@ -28,12 +30,15 @@ static double uni() { return (splitmix() >> 11) * (1.0 / 9007199254740992.0); }
 
 struct Case { const char *name; std::vector<double> s; double b[4]; };
 
-static bool check(const Case &c, bool verbose, bool handover, bool deferred, bool every) {
+static long g_inplace = 0, g_fallback = 0, g_rebase = 0;   // summed over an in-place leg's cases
+
+static bool check(const Case &c, bool verbose, bool handover, bool deferred, bool every, bool inplace) {
     float rx = (float)(c.b[0] - 1.0), ry = (float)(c.b[2] - 1.0);
     float rw = (float)(std::abs(c.b[1] - c.b[0]) + 2.0), rh = (float)(std::abs(c.b[3] - c.b[2]) + 2.0);
     aos::Subdiv2D a, r;
     a.set_handover(handover);
     a.set_deferred(deferred);
+    a.set_inplace(inplace);
     r.set_swap_loop(true);
     const int n = (int)c.s.size() / 2;
     a.reserve(n); r.reserve(n);
@@ -47,6 +52,8 @@ static bool check(const Case &c, bool verbose, bool handover, bool deferred, boo
             return false;
         }
     }
+    if (!inplace && a.n_inplace) { printf("FAIL %s: %ld inserts in place with the switch off\n", c.name, a.n_inplace); return false; }
+    g_inplace += a.n_inplace; g_fallback += a.n_ip_fallback; g_rebase += a.n_rebase;
     if (!deferred && a.n_deferred) { printf("FAIL %s: %ld stars deferred with the switch off\n", c.name, a.n_deferred); return false; }
     std::vector<float> ea, er;
     a.voronoi_edges(ea); r.voronoi_edges(er);
@@ -62,12 +69,12 @@ static bool check(const Case &c, bool verbose, bool handover, bool deferred, boo
     }
 #endif
     if (verbose)
-        printf("ok   %-22s n=%-7d cavity inserts %ld (hand-over %ld, deferred %ld, bailed out %ld, pockets %ld), swap-loop inserts %ld\n",
-               c.name, n, a.n_cavity, a.n_handover, a.n_deferred, a.n_ho_bail, a.n_ho_pocket, a.n_loop);
+        printf("ok   %-22s n=%-7d cavity inserts %ld (hand-over %ld, in place %ld, deferred %ld, bailed out %ld, pockets %ld), swap-loop inserts %ld\n",
+               c.name, n, a.n_cavity, a.n_handover, a.n_inplace, a.n_deferred, a.n_ho_bail, a.n_ho_pocket, a.n_loop);
     return true;
 }
 
-static double time_inserts(const Case &c, bool loop, bool handover, bool deferred, uint64_t &hash) {
+static double time_inserts(const Case &c, bool loop, bool handover, bool deferred, bool inplace, uint64_t &hash) {
     float rx = (float)(c.b[0] - 1.0), ry = (float)(c.b[2] - 1.0);
     float rw = (float)(std::abs(c.b[1] - c.b[0]) + 2.0), rh = (float)(std::abs(c.b[3] - c.b[2]) + 2.0);
     const int n = (int)c.s.size() / 2;
@@ -77,6 +84,7 @@ static double time_inserts(const Case &c, bool loop, bool handover, bool deferre
         sd.set_swap_loop(loop);
         sd.set_handover(handover);
         sd.set_deferred(deferred);
+        sd.set_inplace(inplace);
         sd.reserve(n);
         auto t0 = std::chrono::steady_clock::now();
         sd.init_delaunay(rx, ry, rw, rh, 0);
@@ -152,24 +160,31 @@ int main(int argc, char **argv) {
         cases.push_back(file);
     }
     int fails = 0;
-    // legs: the hand-over with the deferred star (the default path; it needs AVX2) compared after every insert and
+    // legs: the hand-over with the deferred star and the copying walk (it needs AVX2) compared after every insert and
     // only at the end, the hand-over with a ring pass per insert, then the hand-over off (the cavity walk from the
-    // three roots of every insert); each against a swap-loop instance fed in step with it.
-    static const char *const leg[4] = {"hand-over on, star deferred", "hand-over on, star deferred, compared at the end only",
-                                       "hand-over on, ring pass per insert", "hand-over off"};
-    for (int pass = aos::Subdiv2D::simd_ok() ? 0 : 3; pass < 4; ++pass) {
+    // three roots of every insert), then the in-place hand-over (the default path) compared after every insert and only
+    // at the end; each against a swap-loop instance fed in step with it.
+    static const char *const leg[6] = {"hand-over on, star deferred", "hand-over on, star deferred, compared at the end only",
+                                       "hand-over on, ring pass per insert", "hand-over off",
+                                       "in place, star deferred", "in place, star deferred, compared at the end only"};
+    const bool simd = aos::Subdiv2D::simd_ok();
+    for (int pass = simd ? 0 : 3; pass < (simd ? 6 : 4); ++pass) {
+        g_inplace = g_fallback = g_rebase = 0;
         for (size_t i = 0; i < cases.size(); ++i)
-            fails += !check(cases[i], pass == 0 && (i < 6 || i + 1 == cases.size()), pass <= 2, pass <= 1, pass != 1);
+            fails += !check(cases[i], (pass == 0 || pass == 4) && (i < 6 || i + 1 == cases.size()), pass != 3, pass <= 1 || pass >= 4,
+                            pass != 1 && pass != 5, pass >= 4);
+        if (pass >= 4) printf("in place %ld, redone by the copying walk %ld (re-bases %ld)\n", g_inplace, g_fallback, g_rebase);
         printf("%zu cases (%s), %d failed so far\n", cases.size(), leg[pass], fails);
     }
     if (path) {
-        uint64_t hd = 0, hh = 0, hs = 0, hr = 0;
-        const double td = time_inserts(file, false, true, true, hd), th = time_inserts(file, false, true, false, hh),
-                     ts = time_inserts(file, false, false, false, hs), tr = time_inserts(file, true, false, false, hr);
-        const bool eq = hd == hr && hh == hr && hs == hr;
-        printf("%s inserts: deferred %.2f ms, hand-over %.2f ms, hand-over off %.2f ms, swap loop %.2f ms (x%.2f); "
+        uint64_t hi = 0, hd = 0, hh = 0, hs = 0, hr = 0;
+        const double ti = time_inserts(file, false, true, true, true, hi), td = time_inserts(file, false, true, true, false, hd),
+                     th = time_inserts(file, false, true, false, false, hh), ts = time_inserts(file, false, false, false, false, hs),
+                     tr = time_inserts(file, true, false, false, false, hr);
+        const bool eq = hi == hr && hd == hr && hh == hr && hs == hr;
+        printf("%s inserts: in place %.2f ms, deferred %.2f ms, hand-over %.2f ms, hand-over off %.2f ms, swap loop %.2f ms (x%.2f); "
                "facet-edge hash %016llx %s\n",
-               path, td, th, ts, tr, tr / td, (unsigned long long)hd, eq ? "equal" : "DIFFERENT");
+               path, ti, td, th, ts, tr, tr / ti, (unsigned long long)hi, eq ? "equal" : "DIFFERENT");
         if (!eq) fails++;
     }
     return fails ? 1 : 0;

@@ -35,6 +35,10 @@ int main(int argc, char **argv) {
 #ifdef AOS_SD_DEFERRED   // (likewise: an older subdiv2d.h has no deferred star)
     const bool deferred = !getenv("AOS_SD_NO_DEFERRED");   // (set: a ring pass per insert)
 #endif
+#ifdef AOS_SD_INPLACE    // (likewise: an older subdiv2d.h has no in-place hand-over)
+    const bool inplace = !getenv("AOS_SD_NO_INPLACE");     // (set: every hand-over insert copies into the other buffer)
+    long n_inplace = 0, n_ip_fallback = 0, n_rebase = 0;
+#endif
     aos::SdProf bestp{};
     for (int rep = 0; rep < reps; ++rep) {
 #ifdef AOS_SD_PROF
@@ -46,6 +50,9 @@ int main(int argc, char **argv) {
 #endif
 #ifdef AOS_SD_DEFERRED
         sd.set_deferred(deferred);
+#endif
+#ifdef AOS_SD_INPLACE
+        sd.set_inplace(inplace);
 #endif
         sd.reserve(n);
         const auto t0 = std::chrono::steady_clock::now();
@@ -73,6 +80,9 @@ int main(int argc, char **argv) {
 #ifdef AOS_SD_DEFERRED
         n_deferred = sd.n_deferred; n_ho_pocket = sd.n_ho_pocket;
 #endif
+#ifdef AOS_SD_INPLACE
+        n_inplace = sd.n_inplace; n_ip_fallback = sd.n_ip_fallback; n_rebase = sd.n_rebase;
+#endif
         std::vector<float> e;
         sd.voronoi_edges(e);
         hash = 1469598103934665603ull;
@@ -90,6 +100,13 @@ int main(int argc, char **argv) {
            "%.2f kept their spoke",
            bestp.star_loc, bestp.star_found, bestp.star_loc ? (double)bestp.star_steps / bestp.star_loc : 0.0,
            n_handover ? (double)bestp.ring_slots / n_handover : 0.0, n_handover ? (double)bestp.kept_slots / n_handover : 0.0);
+#endif
+#endif
+#ifdef AOS_SD_INPLACE
+    printf(" | in place %ld, redone by the copying walk %ld (re-bases %ld)", n_inplace, n_ip_fallback, n_rebase);
+#ifdef AOS_SD_PROF
+    printf(" (%llu of those in place with a chain across the seam): seam %llu, swapped links %llu, no room %llu; in-place walks that bailed out %llu; %.2f ring slots written per hand-over insert",
+           bestp.ip_unwrapped, bestp.ip_seam, bestp.ip_interior, bestp.ip_rebase, bestp.ip_bail, n_handover ? (double)bestp.ho_slots_written / n_handover : 0.0);
 #endif
 #endif
     printf("\n");
