@@ -2,8 +2,9 @@
 // release() (seedgen.hip) stops the threads and destroys the streams and events first.
 // Methods by file: seedgen.hip the frame (release, run_seedgen*, the thinning driver, the grid copies, finish_frame,
 // debug_grid); cloud_upload.hip the cloud upload, the prefetch and the streaming map's ingest; ror_stage.hip the
-// ROR stage; tiled.hip the tiled frame; gvd_handle.hip the GVD; path.hip the planner (linearize.hip, clearance.hip
-// and regions.hip have no method: their state hangs off lin_state, clear_state and regions_state).
+// ROR stage; tiled.hip the tiled frame; gvd_handle.hip the GVD and the planner calls' graph and grid (plan_graph,
+// plan_grid); path.hip the planner (linearize.hip, clearance.hip and regions.hip have no method: their states are the
+// OwnedState members lin_state, clear_state and regions_state).
 #pragma once
 #include <array>
 #include <condition_variable>
@@ -226,19 +227,23 @@ struct aos_ctx {
     void gvd_async_start();
     bool gvd_async_wait(bool rethrow);   // aos_gvd_wait: collect the oldest job; false if none
     void gvd_view_settle();              // markers / planning: settle which result is current
+    // The planner calls' inputs, from their arguments or from the current result (aos_path_plan, aos_gvd_clearance,
+    // aos_gvd_regions; each settles by its own rule first). graph null: the handle's own graph, with (key, gen) for
+    // the planner's graph cache; throws without one. grid null: the current result's skeleton; a host grid is copied
+    // into staging on the handle's stream.
+    struct PlanGraph { aos_path_graph g; const void *key; uint64_t gen; };
+    struct PlanGrid { const int8_t *d_grid; aos_grid_info info; };
+    PlanGraph plan_graph(const aos_path_graph *graph);
+    PlanGrid plan_grid(const int8_t *grid, int on_device, const aos_grid_info *info, aos::DevBuf &staging);
     void gvd_async_drop();               // a synchronous GVD call supersedes every job in flight
     void gvd_async_stop();
     void lane_join(int l);               // waits for lane l's job (no bookkeeping)
     void lane_apply(int l);              // lane l's finished job becomes the current result
 
-    // ---- path planning (path.hip)
-    void *path_state = nullptr;   // aos::PathState
-    // ---- /aos/path -> /plan (linearize.hip)
-    void *lin_state = nullptr;    // aos::LinState
-    // ---- distance field and GvdGraph clearances (clearance.hip)
-    void *clear_state = nullptr;  // aos::ClearState
-    // ---- nearest-obstacle regions and the grid GVD ridge (regions.hip)
-    void *regions_state = nullptr;  // aos::RegionsState
+    // ---- the planner calls' states, each defined in its file and created on first use: path planning (path.hip:
+    // PathState), /aos/path -> /plan (linearize.hip: LinState), the distance field and GvdGraph clearances
+    // (clearance.hip: ClearState), nearest-obstacle regions and the grid GVD ridge (regions.hip: RegionsState)
+    aos::OwnedState path_state, lin_state, clear_state, regions_state;
 
     // ---- cloud upload, prefetch and streaming map ingest (cloud_upload.hip)
     void set_cloud(const aos_cloud_view &v);

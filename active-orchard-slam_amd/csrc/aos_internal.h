@@ -2,11 +2,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <new>
+#include <stdexcept>
 #include <string>
 #include <utility>
 #include <vector>
@@ -23,6 +25,30 @@ struct HipError { hipError_t e; const char *what; int line; };
         hipError_t _e = (x);                                              \
         if (_e != hipSuccess) throw ::aos::HipError{_e, #x, __LINE__};    \
     } while (0)
+struct CommError { std::string what; };   // a collective failed (tiled.hip, rccl_comm.hip)
+
+inline int fail(int code, const std::string &msg) { set_error(msg); return code; }
+// The one place where an exception becomes an AOS_E_* code and a message: an extern "C" call runs its body as f,
+// whose return value is the call's. where: the file's word in the HIP message; call: the prefix "<call>: " of a
+// thrown message, null: "invalid argument: " / "error: ".
+template <class F> int guarded(const char *where, const char *call, F &&f) {
+    try {
+        return f();
+    } catch (const HipError &e) {
+        return fail(AOS_E_HIP, std::string("HIP error ") + hipGetErrorString(e.e) + " at " + where + " line " +
+                                   std::to_string(e.line) + ": " + e.what);
+    } catch (const std::bad_alloc &) {
+        return fail(AOS_E_NOMEM, "out of host memory");
+    } catch (const CommError &e) {
+        return fail(AOS_E_RCCL, "communicator error: " + e.what);
+    } catch (const std::invalid_argument &e) {
+        return fail(AOS_E_INVALID, (call ? std::string(call) + ": " : std::string("invalid argument: ")) + e.what());
+    } catch (const std::exception &e) {
+        return fail(AOS_E_STATE, (call ? std::string(call) + ": " : std::string("error: ")) + e.what());
+    }
+}
+
+inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // Makes a device current for one scope and restores the caller's device afterwards (also on an
 // exception), so a multi-GPU caller (e.g. torch with one device per thread) keeps its own device.
@@ -79,8 +105,30 @@ struct DevBuf {
         if (trace_on()) trace_alloc("device", c, t0);
         return p;
     }
+    // room for n elements of T (at least one, so the pointer is never null)
+    template <class T> T *ensure_n(size_t n) { return static_cast<T *>(ensure(sizeof(T) * std::max<size_t>(n, 1))); }
     template <class T> T *as() const { return static_cast<T *>(p); }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
+// A state that one file defines and the handle owns (PathState, LinState, ClearState, RegionsState): get<T>()
+// creates it on first use and sets the deleter with it, so aos_ctx needs no declaration of T.
+struct OwnedState {
+    void *p = nullptr;
+    void (*del)(void *) = nullptr;
+    OwnedState() = default;
+    OwnedState(const OwnedState &) = delete;
+    OwnedState &operator=(const OwnedState &) = delete;
+    ~OwnedState() { reset(); }
+    template <class T> T &get() {
+        if (!p) {
+            p = new T();
+            del = [](void *q) { delete static_cast<T *>(q); };
+        }
+        return *static_cast<T *>(p);
+    }
+    template <class T> T *peek() const { return static_cast<T *>(p); }   // null before the first get<T>()
+    void reset() { if (p) del(p); p = nullptr; }
 };
 
 struct PinnedBuf {
@@ -184,7 +232,6 @@ Poly default_polygon();
 int thin_iterations(const int *flags, int iters_run);
 
 // ------------------------------------------------------------------ tiled frames (tiled.hip)
-struct CommError { std::string what; };
 // aos_debug_faults (test hooks): the tiled rank that reports a stuck ROR look-back (-1: none), and the
 // cluster exchange's round-size cap in bytes (0: none)
 extern std::atomic<int> g_debug_stuck_rank;
@@ -211,12 +258,8 @@ struct TilePlan {
     float box[4];               // x/y box of the points this rank needs (xmin, ymin, xmax, ymax)
     uint64_t exchange_bytes;    // per-rank all-gather chunk
 };
-void free_path_state(void *p);   // path.hip
 // the poses (x, y, qz, qw) of the last aos_path_plan on the state (none after "Failed"); false: no plan has run
-bool path_last_poses(const void *path_state, const double **poses, int *n);   // path.hip
-void free_lin_state(void *p);    // linearize.hip
-void free_clear_state(void *p);  // clearance.hip
-void free_regions_state(void *p);   // regions.hip
+bool path_last_poses(const OwnedState &path_state, const double **poses, int *n);   // path.hip
 // The distance field's buffers and launches (clearance.hip), shared with regions.hip, which runs them on its own
 // buffers: masks / up / down = the (64-row band, column) occupancy words and the nearest occupied row above / below
 // each band; g = the column distances; d2 = the field; stats = the occupied count (8 bytes) and the maximum.

@@ -31,33 +31,20 @@
 #include "aos_ctx.h"
 #include "clearance.h"
 #include "dev_prims_device.h"
+#include "field_passes.h"
 
 namespace aos {
 
-// (tests/clearance_scenes.py names these sizes: its sweeps run +-1 around each)
-constexpr int kClrBand = 64;       // rows per band: one bit per row of a (band, column) word
-constexpr int kClrTB = 256;        // threads per workgroup, every kernel here
-constexpr int kClrBlock = 64;      // columns per block minimum of the row pass (a wave's cells)
+// (the band, workgroup and block sizes: field_passes.h)
 constexpr int kClrPer = 8;         // consecutive samples a thread takes per round (k_occupancy's kOccPer)
 
-static inline int clr_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
-
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, o));
-    return v;
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o));
-    return v;
-}
-
 // masks[b * W + x]: bit r = cell (x, b * 64 + r) is occupied. grid (cdiv(W, 256), bands)
-__global__ void __launch_bounds__(kClrTB) k_clr_bands(const int8_t *grid, int W, int H, unsigned long long *masks,
-                                                      unsigned long long *n_occ) {
-    const int x = blockIdx.x * kClrTB + threadIdx.x, b = blockIdx.y;
+__global__ void __launch_bounds__(kFieldTB) k_clr_bands(const int8_t *grid, int W, int H, unsigned long long *masks,
+                                                        unsigned long long *n_occ) {
+    const int x = blockIdx.x * kFieldTB + threadIdx.x, b = blockIdx.y;
     unsigned long long m = 0;
     if (x < W) {
-        const int y0 = b * kClrBand, rows = min(kClrBand, H - y0);
+        const int y0 = b * kFieldBand, rows = min(kFieldBand, H - y0);
         const int8_t *p = grid + (size_t)y0 * W + x;
         for (int r = 0; r < rows; ++r)
             if (p[(size_t)r * W] == 100) m |= 1ull << r;
@@ -69,98 +56,63 @@ __global__ void __launch_bounds__(kClrTB) k_clr_bands(const int8_t *grid, int W,
 }
 
 // up[b * W + x] / down[b * W + x]: the column's nearest occupied row above / below band b (-1: none)
-__global__ void __launch_bounds__(kClrTB) k_clr_carry(const unsigned long long *masks, int W, int nb, int *up, int *down) {
-    const int x = blockIdx.x * kClrTB + threadIdx.x;
+__global__ void __launch_bounds__(kFieldTB) k_clr_carry(const unsigned long long *masks, int W, int nb, int *up, int *down) {
+    const int x = blockIdx.x * kFieldTB + threadIdx.x;
     if (x >= W) return;
     int last = -1;
     for (int b = 0; b < nb; ++b) {
         up[(size_t)b * W + x] = last;
         const unsigned long long m = masks[(size_t)b * W + x];
-        if (m) last = b * kClrBand + 63 - __clzll((long long)m);
+        if (m) last = b * kFieldBand + 63 - __clzll((long long)m);
     }
     last = -1;
     for (int b = nb - 1; b >= 0; --b) {
         down[(size_t)b * W + x] = last;
         const unsigned long long m = masks[(size_t)b * W + x];
-        if (m) last = b * kClrBand + __ffsll((long long)m) - 1;
+        if (m) last = b * kFieldBand + __ffsll((long long)m) - 1;
     }
 }
 
 // g[y * W + x] = min over the column's occupied rows y' of |y - y'|, kColNone without one. grid as k_clr_bands
-__global__ void __launch_bounds__(kClrTB) k_clr_cols(const unsigned long long *masks, const int *up, const int *down, int W,
-                                                     int H, uint16_t *g) {
-    const int x = blockIdx.x * kClrTB + threadIdx.x, b = blockIdx.y;
+__global__ void __launch_bounds__(kFieldTB) k_clr_cols(const unsigned long long *masks, const int *up, const int *down, int W,
+                                                       int H, uint16_t *g) {
+    const int x = blockIdx.x * kFieldTB + threadIdx.x, b = blockIdx.y;
     if (x >= W) return;
     const unsigned long long m = masks[(size_t)b * W + x];
     const int cu = up[(size_t)b * W + x], cd = down[(size_t)b * W + x];
-    const int y0 = b * kClrBand, rows = min(kClrBand, H - y0);
+    const int y0 = b * kFieldBand, rows = min(kFieldBand, H - y0);
     for (int r = 0; r < rows; ++r) {
         const int y = y0 + r;
-        const unsigned long long lo = m & (~0ull >> (63 - r)), hi = m & (~0ull << r);
-        const int above = lo ? y0 + 63 - __clzll((long long)lo) : cu;
-        const int below = hi ? y0 + __ffsll((long long)hi) - 1 : cd;
+        const NearestRows n = band_nearest_rows(m, cu, cd, y0, r);
         int d = clr::kColNone;
-        if (above >= 0) d = y - above;
-        if (below >= 0) d = min(d, below - y);
+        if (n.above >= 0) d = y - n.above;
+        if (n.below >= 0) d = min(d, n.below - y);
         g[(size_t)y * W + x] = (uint16_t)d;
     }
 }
 
+// field_row_pass on the column distances: a candidate is its d2 alone, so a bound equal to the best cannot win
+struct ClrRowPass {
+    typedef uint16_t Stored;
+    static constexpr Stored kNone = clr::kColNone;
+    static constexpr bool kTies = false;
+    struct Cand { unsigned d2 = clr::kNone; };
+    static __device__ __forceinline__ unsigned mag(int v) { return (unsigned)v; }
+    static __device__ __forceinline__ void update(Cand &c, unsigned gv, int x, int xp, int, int) {
+        const unsigned dx = (unsigned)abs(x - xp);
+        const unsigned v = gv == clr::kColNone ? clr::kNone : dx * dx + gv * gv;
+        c.d2 = min(c.d2, v);
+    }
+};
+
 // One workgroup per row. max_d2: the field's maximum (atomicMax per wave).
-__global__ void __launch_bounds__(kClrTB) k_clr_rows(const uint16_t *g, int W, uint32_t *d2, unsigned *max_d2) {
-    __shared__ uint16_t gs[clr::kMaxDim];
-    __shared__ uint16_t bmin[clr::kMaxDim / kClrBlock];
-    const int y = blockIdx.x, tid = threadIdx.x;
-    const uint16_t *gr = g + (size_t)y * W;
-    for (int x0 = 0; x0 < W; x0 += kClrTB) {   // (uniform bounds: every lane takes part in the wave minimum)
-        const int x = x0 + tid;
-        const unsigned v = x < W ? gr[x] : clr::kColNone;
-        if (x < W) gs[x] = (uint16_t)v;
-        const unsigned wm = wave_min_u32(v);
-        if ((tid & 63) == 0 && x < W) bmin[x / kClrBlock] = (uint16_t)wm;
-    }
-    __syncthreads();
-    const int nblk = (W + kClrBlock - 1) / kClrBlock;
-    unsigned row_max = 0;
-    for (int x = tid; x < W; x += kClrTB) {
-        unsigned best = clr::kNone;
-        auto scan = [&](int B) {
-            const int a = B * kClrBlock, e = min(W, a + kClrBlock);
-            for (int xp = a; xp < e; ++xp) {
-                const unsigned gv = gs[xp];
-                const unsigned dx = (unsigned)abs(x - xp);
-                const unsigned v = gv == clr::kColNone ? clr::kNone : dx * dx + gv * gv;
-                best = min(best, v);
-            }
-        };
-        const int bx = x / kClrBlock;
-        scan(bx);
-        for (int k = 1;; ++k) {
-            const int bl = bx - k, br = bx + k;
-            bool any = false;
-            if (bl >= 0) {
-                const unsigned db = (unsigned)(x - (bl * kClrBlock + kClrBlock - 1));
-                if (db * db < best) {
-                    any = true;
-                    const unsigned gm = bmin[bl];
-                    if (gm != clr::kColNone && db * db + gm * gm < best) scan(bl);
-                }
-            }
-            if (br < nblk) {
-                const unsigned db = (unsigned)(br * kClrBlock - x);
-                if (db * db < best) {
-                    any = true;
-                    const unsigned gm = bmin[br];
-                    if (gm != clr::kColNone && db * db + gm * gm < best) scan(br);
-                }
-            }
-            if (!any) break;
-        }
-        d2[(size_t)y * W + x] = best;
-        row_max = max(row_max, best);
-    }
+__global__ void __launch_bounds__(kFieldTB) k_clr_rows(const uint16_t *g, int W, uint32_t *d2, unsigned *max_d2) {
+    const int y = blockIdx.x;
+    unsigned row_max = field_row_pass<ClrRowPass>(g + (size_t)y * W, y, W, [&](int x, const ClrRowPass::Cand &c) {
+        d2[(size_t)y * W + x] = c.d2;
+    });
     row_max = wave_max_u32(row_max);
-    if ((tid & 63) == 0) atomicMax(max_d2, row_max);
+    if ((threadIdx.x & 63) == 0) atomicMax(max_d2, row_max);
 }
 
 __device__ __forceinline__ uint32_t clr_at(const uint32_t *d2, const clr::Grid &g, double px, double py) {
@@ -171,13 +123,13 @@ __device__ __forceinline__ uint32_t clr_at(const uint32_t *d2, const clr::Grid &
 // Workgroups [0, nbn) take 256 nodes each, one per thread; the others 256 edges each. node_out / edge_out: pinned
 // host memory. stats (nullable): the field's occupied count and maximum, copied to h_stats[0 .. 2] (count low,
 // count high, maximum) by the first thread.
-__global__ void __launch_bounds__(kClrTB) k_clr_sample(clr::Grid g, const uint32_t *d2, const double2 *nodes, int n_nodes,
-                                                       const int2 *edges, int n_edges, int nbn, uint32_t *node_out,
-                                                       uint32_t *edge_out, const unsigned long long *n_occ,
-                                                       const unsigned *max_d2, uint32_t *h_stats) {
-    __shared__ int pre[kClrTB + 1], wsum[kClrTB / 64], tot_s;
-    __shared__ unsigned best_s[kClrTB];
-    __shared__ clr::Edge e_s[kClrTB];
+__global__ void __launch_bounds__(kFieldTB) k_clr_sample(clr::Grid g, const uint32_t *d2, const double2 *nodes, int n_nodes,
+                                                         const int2 *edges, int n_edges, int nbn, uint32_t *node_out,
+                                                         uint32_t *edge_out, const unsigned long long *n_occ,
+                                                         const unsigned *max_d2, uint32_t *h_stats) {
+    __shared__ int pre[kFieldTB + 1], wsum[kFieldTB / 64], tot_s;
+    __shared__ unsigned best_s[kFieldTB];
+    __shared__ clr::Edge e_s[kFieldTB];
     const int tid = threadIdx.x;
     if (blockIdx.x == 0 && tid == 0 && h_stats) {
         const unsigned long long n = *n_occ;
@@ -186,14 +138,14 @@ __global__ void __launch_bounds__(kClrTB) k_clr_sample(clr::Grid g, const uint32
         h_stats[2] = *max_d2;
     }
     if ((int)blockIdx.x < nbn) {
-        const int i = blockIdx.x * kClrTB + tid;
+        const int i = blockIdx.x * kFieldTB + tid;
         if (i < n_nodes) {
             const double2 p = nodes[i];
             node_out[i] = clr_at(d2, g, p.x, p.y);
         }
         return;
     }
-    const int c = ((int)blockIdx.x - nbn) * kClrTB + tid;
+    const int c = ((int)blockIdx.x - nbn) * kFieldTB + tid;
     int nsamp = 0;
     unsigned first = clr::kNone;
     if (c < n_edges) {
@@ -209,16 +161,16 @@ __global__ void __launch_bounds__(kClrTB) k_clr_sample(clr::Grid g, const uint32
         }
     }
     best_s[tid] = first;
-    const int before = block_excl_scan<kClrTB>(nsamp, wsum, &tot_s);   // (synchronises)
+    const int before = block_excl_scan<kFieldTB>(nsamp, wsum, &tot_s);   // (synchronises)
     pre[tid] = before;
-    if (tid == 0) pre[kClrTB] = tot_s;
+    if (tid == 0) pre[kFieldTB] = tot_s;
     __syncthreads();
-    const int T = pre[kClrTB];
-    for (int q0 = 0; q0 < T; q0 += kClrTB * kClrPer) {
+    const int T = pre[kFieldTB];
+    for (int q0 = 0; q0 < T; q0 += kFieldTB * kClrPer) {
         // the thread's kClrPer consecutive samples: one search for the first one's edge, then forward
         const int qb = q0 + tid * kClrPer;
         if (qb >= T) continue;
-        int lo = 0, hi = kClrTB - 1;   // the edge o with pre[o] <= qb < pre[o + 1]
+        int lo = 0, hi = kFieldTB - 1;   // the edge o with pre[o] <= qb < pre[o + 1]
         while (lo < hi) {
             const int mid = (lo + hi + 1) >> 1;
             if (pre[mid] <= qb) lo = mid; else hi = mid - 1;
@@ -232,7 +184,7 @@ __global__ void __launch_bounds__(kClrTB) k_clr_sample(clr::Grid g, const uint32
             v[u] = clr::kNone;
             oo[u] = -1;
             if (q >= T) continue;
-            while (pre[o + 1] <= q) ++o;   // (q < T = pre[kClrTB]: o stays below kClrTB)
+            while (pre[o + 1] <= q) ++o;   // (q < T = pre[kFieldTB]: o stays below kFieldTB)
             oo[u] = o;
             double px, py;
             clr::sample_point(e_s[o], e_s[o].i0 + (q - pre[o]), px, py);
@@ -260,59 +212,43 @@ struct ClearState {
     }
 };
 
-void free_clear_state(void *p) { delete static_cast<ClearState *>(p); }
-
-template <class T> static T *clr_dev(DevBuf &b, size_t n) { return static_cast<T *>(b.ensure(sizeof(T) * std::max<size_t>(n, 1))); }
-
 // the band words and the carries of d_grid (W, H >= 1); *n_occ += the occupied count (regions.hip shares these two)
 void clr_launch_bands(ClrFieldBufs &B, const int8_t *d_grid, int W, int H, unsigned long long *n_occ, hipStream_t s) {
-    const int nb = clr_cdiv(H, kClrBand);
-    auto *masks = clr_dev<unsigned long long>(B.masks, (size_t)nb * W);
-    int *up = clr_dev<int>(B.up, (size_t)nb * W), *down = clr_dev<int>(B.down, (size_t)nb * W);
-    k_clr_bands<<<dim3(clr_cdiv(W, kClrTB), nb), kClrTB, 0, s>>>(d_grid, W, H, masks, n_occ);
-    k_clr_carry<<<clr_cdiv(W, kClrTB), kClrTB, 0, s>>>(masks, W, nb, up, down);
+    const int nb = cdiv(H, kFieldBand);
+    auto *masks = B.masks.ensure_n<unsigned long long>((size_t)nb * W);
+    int *up = B.up.ensure_n<int>((size_t)nb * W), *down = B.down.ensure_n<int>((size_t)nb * W);
+    k_clr_bands<<<dim3(cdiv(W, kFieldTB), nb), kFieldTB, 0, s>>>(d_grid, W, H, masks, n_occ);
+    k_clr_carry<<<cdiv(W, kFieldTB), kFieldTB, 0, s>>>(masks, W, nb, up, down);
 }
 
 // the three field passes on d_grid (W, H >= 1) into B.d2; B.stats: the occupied count (8 bytes), the maximum
 void clr_launch_field(ClrFieldBufs &B, const int8_t *d_grid, int W, int H, hipStream_t s) {
     const size_t C = (size_t)W * H;
-    const int nb = clr_cdiv(H, kClrBand);
-    uint16_t *g = clr_dev<uint16_t>(B.g, C);
-    uint32_t *d2 = clr_dev<uint32_t>(B.d2, C);
-    char *st = clr_dev<char>(B.stats, 16);
+    const int nb = cdiv(H, kFieldBand);
+    uint16_t *g = B.g.ensure_n<uint16_t>(C);
+    uint32_t *d2 = B.d2.ensure_n<uint32_t>(C);
+    char *st = B.stats.ensure_n<char>(16);
     AOS_HIP(hipMemsetAsync(st, 0, 16, s));
     clr_launch_bands(B, d_grid, W, H, reinterpret_cast<unsigned long long *>(st), s);
-    k_clr_cols<<<dim3(clr_cdiv(W, kClrTB), nb), kClrTB, 0, s>>>(B.masks.as<unsigned long long>(), B.up.as<int>(),
+    k_clr_cols<<<dim3(cdiv(W, kFieldTB), nb), kFieldTB, 0, s>>>(B.masks.as<unsigned long long>(), B.up.as<int>(),
                                                                  B.down.as<int>(), W, H, g);
-    k_clr_rows<<<H, kClrTB, 0, s>>>(g, W, d2, reinterpret_cast<unsigned *>(st + 8));
+    k_clr_rows<<<H, kFieldTB, 0, s>>>(g, W, d2, reinterpret_cast<unsigned *>(st + 8));
     AOS_HIP(hipGetLastError());
 }
 
 namespace {
 
 ClearState &clear_state(aos_ctx *c) {
-    if (!c->clear_state) c->clear_state = new ClearState();
-    ClearState &S = *static_cast<ClearState *>(c->clear_state);
+    ClearState &S = c->clear_state.get<ClearState>();
     for (hipEvent_t &e : S.ev) if (!e) AOS_HIP(hipEventCreate(&e));
     return S;
 }
-
-int fail(int code, const std::string &msg) { set_error(msg); return code; }
 
 }  // namespace
 
 }  // namespace aos
 
 using namespace aos;
-
-#define AOS_CLR_CATCH(tag)                                                                                           \
-    catch (const HipError &e) {                                                                                      \
-        return fail(AOS_E_HIP, std::string("HIP error ") + hipGetErrorString(e.e) + " at clearance line " +          \
-                                   std::to_string(e.line) + ": " + e.what);                                          \
-    }                                                                                                                \
-    catch (const std::bad_alloc &) { return fail(AOS_E_NOMEM, "out of host memory"); }                               \
-    catch (const std::invalid_argument &e) { return fail(AOS_E_INVALID, std::string(tag ": ") + e.what()); }        \
-    catch (const std::exception &e) { return fail(AOS_E_STATE, std::string(tag ": ") + e.what()); }
 
 extern "C" int aos_gvd_clearance(aos_ctx *c, const aos_path_graph *graph, const int8_t *grid, int grid_on_device,
                                  const aos_grid_info *info, aos_clearance_out *out) {
@@ -323,44 +259,22 @@ extern "C" int aos_gvd_clearance(aos_ctx *c, const aos_path_graph *graph, const 
     if (graph)
         if (const char *m = clr::check_graph(graph->nodes_xy, graph->num_nodes, graph->edges, graph->num_edges))
             return fail(AOS_E_INVALID, std::string("aos_gvd_clearance: ") + m);
-    try {
+    return guarded("clearance", "aos_gvd_clearance", [&]() -> int {
         DeviceScope dev_scope(c->device);
         if (!graph || !grid) c->gvd_view_settle();
-        // the graph: only its nodes and edges are read
-        const double *nodes_xy;
-        const int32_t *edges;
-        int32_t nn, ne;
-        if (graph) {
-            nodes_xy = graph->nodes_xy; edges = graph->edges; nn = graph->num_nodes; ne = graph->num_edges;
-        } else {
-            if (!c->have_gvd) throw std::runtime_error("no GVD graph on this handle");
-            GvdState &gs = c->gs();
-            markers_wait(gs, false);
-            nodes_xy = gs.nodes_xy.data(); edges = gs.edges_out.data();
-            nn = (int32_t)gs.labels.size(); ne = (int32_t)gs.lengths.size();
+        // the graph (only its nodes and edges are read) and the grid; the handle's own are checked like a caller's
+        const aos_path_graph g = c->plan_graph(graph).g;
+        const double *nodes_xy = g.nodes_xy;
+        const int32_t *edges = g.edges;
+        const int32_t nn = g.num_nodes, ne = g.num_edges;
+        if (!graph)
             if (const char *m = clr::check_graph(nodes_xy, nn, edges, ne)) throw std::invalid_argument(m);
-        }
         ClearState &S = clear_state(c);
-        // the grid (device)
-        const int8_t *d_grid = nullptr;
-        aos_grid_info gi{};
-        if (grid) {
-            gi = *info;
-            const size_t C = (size_t)gi.width * gi.height;
-            if (grid_on_device) d_grid = grid;
-            else if (C) {
-                int8_t *d = clr_dev<int8_t>(S.d_grid, C);
-                AOS_HIP(hipMemcpyAsync(d, grid, C, hipMemcpyHostToDevice, c->stream));
-                d_grid = d;
-            }
-        } else {
-            if (!c->have_gvd) throw std::runtime_error("no grid given and no GVD call on this handle");
-            if (c->gvd_from_frame && c->gvd_frame_gen != c->frame_gen)
-                throw std::runtime_error("the GVD graph's skeleton was replaced by a later seed-gen frame; pass the grid");
-            d_grid = c->gvd_skel;
-            gi = c->gvd_info;
+        const aos_ctx::PlanGrid pg = c->plan_grid(grid, grid_on_device, info, S.d_grid);
+        const int8_t *d_grid = pg.d_grid;
+        const aos_grid_info gi = pg.info;
+        if (!grid)
             if (const char *m = clr::check_info(gi)) throw std::invalid_argument(m);
-        }
         S.have_field = false;
         S.info = gi;
         S.g = clr::Grid{gi.origin_x, gi.origin_y, (double)gi.resolution, (int)gi.width, (int)gi.height};
@@ -375,16 +289,16 @@ extern "C" int aos_gvd_clearance(aos_ctx *c, const aos_path_graph *graph, const 
             h_stats[0] = h_stats[1] = 0;
             h_stats[2] = clr::kNone;
         } else {
-            double2 *d_nodes = clr_dev<double2>(S.d_nodes, nn);
-            int2 *d_edges = clr_dev<int2>(S.d_edges, ne);
+            double2 *d_nodes = S.d_nodes.ensure_n<double2>(nn);
+            int2 *d_edges = S.d_edges.ensure_n<int2>(ne);
             if (nn) AOS_HIP(hipMemcpyAsync(d_nodes, nodes_xy, sizeof(double2) * (size_t)nn, hipMemcpyHostToDevice, c->stream));
             if (ne) AOS_HIP(hipMemcpyAsync(d_edges, edges, sizeof(int2) * (size_t)ne, hipMemcpyHostToDevice, c->stream));
             AOS_HIP(hipEventRecord(S.ev[0], c->stream));
             clr_launch_field(S.f, d_grid, S.g.W, S.g.H, c->stream);
             AOS_HIP(hipEventRecord(S.ev[1], c->stream));
-            const int nbn = clr_cdiv(nn, kClrTB), nbe = clr_cdiv(ne, kClrTB);
+            const int nbn = cdiv(nn, kFieldTB), nbe = cdiv(ne, kFieldTB);
             const char *st = S.f.stats.as<char>();
-            k_clr_sample<<<std::max(1, nbn + nbe), kClrTB, 0, c->stream>>>(
+            k_clr_sample<<<std::max(1, nbn + nbe), kFieldTB, 0, c->stream>>>(
                 S.g, S.f.d2.as<uint32_t>(), d_nodes, nn, d_edges, ne, nbn, h_node, h_edge,
                 reinterpret_cast<const unsigned long long *>(st), reinterpret_cast<const unsigned *>(st + 8), h_stats);
             AOS_HIP(hipGetLastError());
@@ -408,44 +322,42 @@ extern "C" int aos_gvd_clearance(aos_ctx *c, const aos_path_graph *graph, const 
         out->node_clearances = S.node_m.data(); out->edge_clearances = S.edge_m.data();
         out->ms_field = ms_field; out->ms_graph = ms_graph;
         return AOS_OK;
-    }
-    AOS_CLR_CATCH("aos_gvd_clearance")
+    });
 }
 
 extern "C" int aos_clearance_field_copy(aos_ctx *c, uint32_t *dst, uint64_t capacity_cells) {
     if (!c) return fail(AOS_E_INVALID, "aos_clearance_field_copy: null handle");
-    const ClearState *S = static_cast<const ClearState *>(c->clear_state);
+    const ClearState *S = c->clear_state.peek<ClearState>();
     if (!S || !S->have_field) return fail(AOS_E_STATE, "aos_clearance_field_copy: no aos_gvd_clearance on this handle yet");
     const uint64_t C = (uint64_t)S->g.W * (uint64_t)S->g.H;
     if (capacity_cells < C) return fail(AOS_E_INVALID, "aos_clearance_field_copy: capacity below width x height");
     if (C && !dst) return fail(AOS_E_INVALID, "aos_clearance_field_copy: null destination");
-    try {
+    return guarded("clearance", "aos_clearance_field_copy", [&]() -> int {
         DeviceScope dev_scope(c->device);
         if (C) {
             AOS_HIP(hipMemcpyAsync(dst, S->f.d2.p, sizeof(uint32_t) * C, hipMemcpyDeviceToHost, c->stream));
             AOS_HIP(hipStreamSynchronize(c->stream));
         }
         return AOS_OK;
-    }
-    AOS_CLR_CATCH("aos_clearance_field_copy")
+    });
 }
 
 extern "C" int aos_clearance_points(aos_ctx *c, const double *xy, int32_t n, uint32_t *d2_out, float *metres_out) {
     if (!c) return fail(AOS_E_INVALID, "aos_clearance_points: null handle");
     if (n < 0) return fail(AOS_E_INVALID, "aos_clearance_points: negative count");
     if (n > 0 && !xy) return fail(AOS_E_INVALID, "aos_clearance_points: null points behind a count above 0");
-    ClearState *S = static_cast<ClearState *>(c->clear_state);
+    ClearState *S = c->clear_state.peek<ClearState>();
     if (!S || !S->have_field) return fail(AOS_E_STATE, "aos_clearance_points: no aos_gvd_clearance on this handle yet");
     if (n == 0) return AOS_OK;
-    try {
+    return guarded("clearance", "aos_clearance_points", [&]() -> int {
         DeviceScope dev_scope(c->device);
         uint32_t *h = static_cast<uint32_t *>(S->h_pts.ensure(sizeof(uint32_t) * (size_t)n));
         if ((size_t)S->g.W * S->g.H == 0) std::fill(h, h + n, clr::kNone);
         else {
-            double2 *d_pts = clr_dev<double2>(S->d_pts, n);
+            double2 *d_pts = S->d_pts.ensure_n<double2>(n);
             AOS_HIP(hipMemcpyAsync(d_pts, xy, sizeof(double2) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-            const int nbn = clr_cdiv(n, kClrTB);
-            k_clr_sample<<<nbn, kClrTB, 0, c->stream>>>(S->g, S->f.d2.as<uint32_t>(), d_pts, n, nullptr, 0, nbn, h, nullptr,
+            const int nbn = cdiv(n, kFieldTB);
+            k_clr_sample<<<nbn, kFieldTB, 0, c->stream>>>(S->g, S->f.d2.as<uint32_t>(), d_pts, n, nullptr, 0, nbn, h, nullptr,
                                                         nullptr, nullptr, nullptr);
             AOS_HIP(hipGetLastError());
             AOS_HIP(hipStreamSynchronize(c->stream));
@@ -453,6 +365,5 @@ extern "C" int aos_clearance_points(aos_ctx *c, const double *xy, int32_t n, uin
         if (d2_out) std::memcpy(d2_out, h, sizeof(uint32_t) * (size_t)n);
         if (metres_out) clr::to_metres(h, n, S->g.res, metres_out);
         return AOS_OK;
-    }
-    AOS_CLR_CATCH("aos_clearance_points")
+    });
 }

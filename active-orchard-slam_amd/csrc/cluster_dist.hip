@@ -36,7 +36,6 @@
 
 namespace aos {
 
-static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // ------------------------------------------------------------------ the rank's own cells (device)
 // Own region of the window skeleton: rows [y0, y0 + nr), words [c0, c0 + nc) of the map, at row oy /
@@ -219,7 +218,6 @@ static void gather_bytes(FrameComm &fc, hipStream_t s, const void *src, bool src
     }
 }
 
-template <class T> static T *dptr(DevBuf &b, size_t n) { return static_cast<T *>(b.ensure(sizeof(T) * std::max<size_t>(n, 1))); }
 template <class T> static T *hptr(PinnedBuf &b, size_t n) { return static_cast<T *>(b.ensure(sizeof(T) * std::max<size_t>(n, 1))); }
 
 struct OwnedOut { int l, replayed; ClusterRec r; };
@@ -239,7 +237,7 @@ static const int *exchange_cells(FrameComm &fc, ClusterDistState &D, hipStream_t
     for (int a = 0; a < W; ++a)
         for (int b = 0; b < W; ++b) { row[a] += cnt[(size_t)a * W + b]; col[b] += cnt[(size_t)a * W + b]; }
     if (!fc.has_all_to_all()) {   // through all_gather: everyone's route buffer, then this rank's blocks from it
-        uint8_t *all = dptr<uint8_t>(D.landing, std::accumulate(row.begin(), row.end(), (uint64_t)0));
+        uint8_t *all = D.landing.ensure_n<uint8_t>(std::accumulate(row.begin(), row.end(), (uint64_t)0));
         gather_bytes(fc, s, send, true, row, all, true, D.h_recv);
         uint64_t at = 0;
         for (int r = 0; r < W; ++r) {
@@ -252,7 +250,7 @@ static const int *exchange_cells(FrameComm &fc, ClusterDistState &D, hipStream_t
     }
     uint64_t roff = 0;
     for (int r = 0; r < W; ++r) { src_base[r] = roff / 4; roff += cnt[(size_t)r * W + me]; }
-    int *land = dptr<int>(D.landing, roff / 4);
+    int *land = D.landing.ensure_n<int>(roff / 4);
     // rounds of at most q bytes per pair keep every row sum <= buf_bytes and column sum <= world * buf_bytes
     uint64_t q = (cm.buf_bytes / (uint64_t)W) & ~7ull;
     const uint64_t q_cap = debug_a2a_round_bytes();   // (tests: force many rounds)
@@ -299,7 +297,7 @@ void cluster_dist(ClusterDistState &D, FrameComm &fc, const TilePlan &t, const F
     const int npoly = (int)poly.size();
     double *hp = hptr<double>(D.h_poly, 2 * (size_t)npoly);
     for (int i = 0; i < npoly; ++i) { hp[2 * i] = poly[i].first; hp[2 * i + 1] = poly[i].second; }
-    double *d_poly = dptr<double>(D.poly, 2 * (size_t)npoly);
+    double *d_poly = D.poly.ensure_n<double>(2 * (size_t)npoly);
     copy_from_host(d_poly, hp, sizeof(double) * 2 * npoly, s);
     TileView T{t.y0, t.y1 - t.y0, t.c0, t.c1 - t.c0, t.y0 - t.wy0, t.c0 - t.wc0, t.lg.WW, 0};
     T.Wt = std::min(W, 64 * t.c1) - 64 * t.c0;
@@ -307,8 +305,8 @@ void cluster_dist(ClusterDistState &D, FrameComm &fc, const TilePlan &t, const F
 
     // ---- 1. own foreground, pieces, border cells (the whole-map stage's labelling on the own region)
     const size_t Cw = (size_t)T.nc * T.nr;
-    uint64_t *d_fg = dptr<uint64_t>(D.fg, Cw);
-    int *d_cnt = dptr<int>(D.cnt, Cw), *d_off = dptr<int>(D.ccl.off, Cw + 1);
+    uint64_t *d_fg = D.fg.ensure_n<uint64_t>(Cw);
+    int *d_cnt = D.cnt.ensure_n<int>(Cw), *d_off = D.ccl.off.ensure_n<int>(Cw + 1);
     k_dist_fg<<<dim3(cdiv(T.nc, 64), T.nr), 64, 0, s>>>(win, T, g, d_poly, npoly, d_fg, d_cnt);
     scan_1p(D.ccl.lb, d_cnt, d_off, (int)Cw, false, s);
     GridC gl{};   // the own region as an image: local raster index = ly * Wt + lx
@@ -318,13 +316,13 @@ void cluster_dist(ClusterDistState &D, FrameComm &fc, const TilePlan &t, const F
     const int *d_list = D.ccl.list_p, *d_par = D.ccl.parent_p, *d_rank = D.ccl.rank_p;
     const int *d_np = d_rank + nf;   // (pieces: on the device)
     const size_t PC = (size_t)std::max(nf, 1);
-    int *pi = dptr<int>(D.pieces, 6 * PC + 4 * PC);
+    int *pi = D.pieces.ensure_n<int>(6 * PC + 4 * PC);
     PieceDev P{pi, pi + PC, pi + 2 * PC, pi + 3 * PC, pi + 4 * PC, pi + 5 * PC,
                reinterpret_cast<unsigned long long *>(pi + 6 * PC), reinterpret_cast<unsigned long long *>(pi + 8 * PC)};
-    int *d_pid = dptr<int>(D.pid, PC), *d_prank = dptr<int>(D.prank, PC);
-    int2 *d_border = dptr<int2>(D.border, PC);
-    int *d_nb = dptr<int>(D.counts, 2);
-    uint8_t *d_blob = dptr<uint8_t>(D.blob, (sizeof(PieceRec) + sizeof(int2)) * PC);
+    int *d_pid = D.pid.ensure_n<int>(PC), *d_prank = D.prank.ensure_n<int>(PC);
+    int2 *d_border = D.border.ensure_n<int2>(PC);
+    int *d_nb = D.counts.ensure_n<int>(2);
+    uint8_t *d_blob = D.blob.ensure_n<uint8_t>((sizeof(PieceRec) + sizeof(int2)) * PC);
     if (nf > 0) {
         k_piece_init<<<cdiv(nf, 256), 256, 0, s>>>(P, d_np, nf, d_nb);
         k_piece_agg<<<cdiv(nf, kPcTB), kPcTB, 0, s>>>(d_list, d_par, d_rank, nf, T, W, g.H, P, d_pid, d_prank, d_border, d_nb);
@@ -428,11 +426,11 @@ void cluster_dist(ClusterDistState &D, FrameComm &fc, const TilePlan &t, const F
             }
         // ---- route the own cells of long pieces into the send layout
         const long long my_send = rank_at[me];
-        int *d_send = dptr<int>(D.sendbuf, (size_t)my_send);
+        int *d_send = D.sendbuf.ensure_n<int>((size_t)my_send);
         if (my_send > 0) {
             int *hpo = hptr<int>(D.h_poff, (size_t)npieces);
             for (int p = 0; p < npieces; ++p) hpo[p] = (int)piece_off[rp0[me] + p];
-            int *d_poff = dptr<int>(D.poff, (size_t)npieces);
+            int *d_poff = D.poff.ensure_n<int>((size_t)npieces);
             copy_from_host(d_poff, hpo, sizeof(int) * npieces, s);
             k_route<<<cdiv(nf, 256), 256, 0, s>>>(d_list, d_pid, d_prank, nf, d_poff, T, W, d_send);
             AOS_HIP(hipGetLastError());
@@ -467,15 +465,15 @@ void cluster_dist(ClusterDistState &D, FrameComm &fc, const TilePlan &t, const F
         if (nown > 0) {
             Seg *hs = hptr<Seg>(D.h_segs, segs.size());
             std::copy(segs.begin(), segs.end(), hs);
-            Seg *d_segs = dptr<Seg>(D.segs, segs.size());
+            Seg *d_segs = D.segs.ensure_n<Seg>(segs.size());
             copy_from_host(d_segs, hs, sizeof(Seg) * segs.size(), s);
             int *hco = hptr<int>(D.h_coff, (size_t)nown + 1);
             std::copy(coff.begin(), coff.end(), hco);
-            int *d_coff = dptr<int>(D.coff, (size_t)nown + 1);
+            int *d_coff = D.coff.ensure_n<int>((size_t)nown + 1);
             copy_from_host(d_coff, hco, sizeof(int) * (nown + 1), s);
-            int *d_cells = dptr<int>(D.cells, (size_t)n_owned_cells);
+            int *d_cells = D.cells.ensure_n<int>((size_t)n_owned_cells);
             k_segments<<<(int)segs.size(), 256, 0, s>>>(d_segs, land, d_cells);
-            ClusterRec *d_rec = dptr<ClusterRec>(D.rec, (size_t)nown);
+            ClusterRec *d_rec = D.rec.ensure_n<ClusterRec>((size_t)nown);
             launch_cluster_stats(d_coff, d_cells, nown, g, d_poly, npoly, min_len, d_rec, s);
             ClusterRec *hr = hptr<ClusterRec>(D.h_rec, (size_t)nown);
             copy_to_host(hr, d_rec, sizeof(ClusterRec) * nown, s);

@@ -27,7 +27,6 @@
 
 namespace aos {
 
-static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // ------------------------------------------------------------------ foreground = skeleton inside polygon
 // The foreground words and their popcounts (k_scan_1p turns them into the words' offsets). (Round 5 measured the
@@ -753,7 +752,6 @@ __global__ void k_concat3(const double2 *a, const double2 *b, const double2 *c, 
 }
 
 // ------------------------------------------------------------------ host orchestration
-template <class T> static T *dev(DevBuf &b, size_t n) { return static_cast<T *>(b.ensure(sizeof(T) * std::max<size_t>(n, 1))); }
 
 // The whole-map stage's labelling on any foreground given as bits (the tiled frame's own region, cluster_dist.hip):
 // list, block-local union-find in LDS, cross-chunk unions, flatten, root ranks. One host wait (for nf); the
@@ -765,23 +763,23 @@ int ccl_label(CclScratch &B, const uint64_t *fg, const int *off, const GridC &g,
     AOS_HIP(hipStreamSynchronize(s));
     *err = h_pinned2[1];
     const int nf = *err ? 0 : h_pinned2[0];
-    B.list_p = dev<int>(B.list, nf);
-    B.parent_p = dev<int>(B.parent, nf);
-    B.rank_p = dev<int>(B.rank, (size_t)nf + 1);
+    B.list_p = B.list.ensure_n<int>(nf);
+    B.parent_p = B.parent.ensure_n<int>(nf);
+    B.rank_p = B.rank.ensure_n<int>((size_t)nf + 1);
     if (nf == 0) {
         AOS_HIP(hipMemsetAsync(B.rank_p, 0, sizeof(int), s));
         return 0;
     }
     const dim3 gw2(cdiv(g.WW, 64), g.H);
     const int ecap = ccl_edge_cap(nf);
-    int *d_ne = dev<int>(B.edges, 2 + 2 * (size_t)ecap);
+    int *d_ne = B.edges.ensure_n<int>(2 + 2 * (size_t)ecap);
     int2 *d_edges = reinterpret_cast<int2 *>(d_ne + 2);
     k_fg_list<<<gw2, 64, 0, s>>>(fg, d_off, B.list_p, g, nullptr, d_ne);
     const int chunk = kCclChunk;
     k_ccl_local<<<cdiv(nf, chunk), kCclTB, sizeof(int) * chunk, s>>>(B.list_p, nf, fg, d_off, g, B.parent_p, d_edges, d_ne,
                                                                       ecap - 1, chunk);
     k_ccl_cross<<<256, 256, 0, s>>>(d_edges, d_ne, ecap - 1, B.parent_p, B.list_p, nf, fg, d_off, g);
-    ccl_flatten_rank(B.lb, B.parent_p, dev<int>(B.isroot, nf), B.rank_p, nf, s);
+    ccl_flatten_rank(B.lb, B.parent_p, B.isroot.ensure_n<int>(nf), B.rank_p, nf, s);
     AOS_HIP(hipGetLastError());
     return nf;
 }
@@ -796,7 +794,7 @@ void run_cluster_seed_stage(ClusterSeedState &S, const SeedStageIn &in, SeedStag
     const Poly &poly = *in.poly;
     const int np = (int)poly.size();
     const size_t pc0 = S.poly.cap;
-    double *d_poly = dev<double>(S.poly, 2 * np);
+    double *d_poly = S.poly.ensure_n<double>(2 * np);
     std::vector<double> hp(2 * np);
     for (int i = 0; i < np; ++i) { hp[2 * i] = poly[i].first; hp[2 * i + 1] = poly[i].second; }
     // host -> device through a pinned staging buffer, only when the polygon (or its buffer) changed
@@ -815,9 +813,9 @@ void run_cluster_seed_stage(ClusterSeedState &S, const SeedStageIn &in, SeedStag
     int *d_wo = nullptr;
     const dim3 gw2(cdiv(g.WW, 64), g.H);
     if (!in.pre) {
-        d_fg = dev<uint64_t>(S.fg_bits, Cw);
-        int *d_wc = dev<int>(S.word_cnt, Cw);
-        d_wo = dev<int>(S.word_off, Cw + 1);
+        d_fg = S.fg_bits.ensure_n<uint64_t>(Cw);
+        int *d_wc = S.word_cnt.ensure_n<int>(Cw);
+        d_wo = S.word_off.ensure_n<int>(Cw + 1);
         k_fg<<<gw2, 64, 0, s>>>(in.skel_bits, d_fg, d_wc, g, d_poly, np);
         scan_1p(S.lb, d_wc, d_wo, (int)Cw, false, s);
         peek_to_host(h_sc, {d_wo + Cw, S.lb.err_word(s)}, s);
@@ -844,10 +842,10 @@ void run_cluster_seed_stage(ClusterSeedState &S, const SeedStageIn &in, SeedStag
         S.n_clusters = (int)S.h_rec.size();
         out.n_bfs = in.pre->n_bfs;
     } else if (nf > 0) {
-        int *d_list = dev<int>(S.fg_list, nf);
-        int *d_par = dev<int>(S.parent, nf), *d_isroot = dev<int>(S.root_flag, nf), *d_rank = dev<int>(S.root_rank, nf + 1);
+        int *d_list = S.fg_list.ensure_n<int>(nf);
+        int *d_par = S.parent.ensure_n<int>(nf), *d_isroot = S.root_flag.ensure_n<int>(nf), *d_rank = S.root_rank.ensure_n<int>(nf + 1);
         const int ecap = ccl_edge_cap(nf);
-        int *d_ne = dev<int>(S.ccl_edges, 2 + 2 * (size_t)ecap);
+        int *d_ne = S.ccl_edges.ensure_n<int>(2 + 2 * (size_t)ecap);
         int2 *d_edges = reinterpret_cast<int2 *>(d_ne + 2);   // (8-byte aligned: DevBuf bases are)
         k_fg_list<<<gw2, 64, 0, s>>>(d_fg, d_wo, d_list, g, nullptr, d_ne);
         const int chunk = kCclChunk;
@@ -863,17 +861,17 @@ void run_cluster_seed_stage(ClusterSeedState &S, const SeedStageIn &in, SeedStag
         S.n_clusters = ncl;
         // bucket the foreground cells by cluster id: counting sort (k_cluster_count)
         const size_t cc0 = S.cl_count.cap;
-        int *d_ccnt = dev<int>(S.cl_count, ncl + 1);
+        int *d_ccnt = S.cl_count.ensure_n<int>(ncl + 1);
         if (S.cl_count.cap != cc0 || S.cl_count_dirty) AOS_HIP(hipMemsetAsync(d_ccnt, 0, S.cl_count.cap, s));
         S.cl_count_dirty = true;
-        int *d_off = dev<int>(S.cl_off, ncl + 1);
-        int *d_cid = dev<int>(S.cl_cursor, 2 * (size_t)nf), *d_crank = d_cid + nf;
-        int *d_cells = dev<int>(S.cl_cells, nf);
+        int *d_off = S.cl_off.ensure_n<int>(ncl + 1);
+        int *d_cid = S.cl_cursor.ensure_n<int>(2 * (size_t)nf), *d_crank = d_cid + nf;
+        int *d_cells = S.cl_cells.ensure_n<int>(nf);
         k_cluster_count<<<cdiv(nf, kClTB), kClTB, 0, s>>>(d_par, d_rank, nf, d_cid, d_crank, d_ccnt);
         scan_1p(S.lb, d_ccnt, d_off, ncl, true, s);   // (leaves the counts zero)
         S.cl_count_dirty = false;
         k_cluster_scatter<<<cdiv(nf, 256), 256, 0, s>>>(d_list, d_cid, d_crank, d_off, nf, d_cells);
-        ClusterRec *d_rec = dev<ClusterRec>(S.rec, ncl);
+        ClusterRec *d_rec = S.rec.ensure_n<ClusterRec>(ncl);
         S.h_rec.resize(ncl);
         ClusterRec *hr = static_cast<ClusterRec *>(S.h_recbuf.ensure(sizeof(ClusterRec) * (size_t)ncl));
         launch_cluster_stats(d_off, d_cells, ncl, g, d_poly, np, static_cast<float>(in.cluster_min_length), d_rec, s, hr);
@@ -916,9 +914,9 @@ void run_cluster_seed_stage(ClusterSeedState &S, const SeedStageIn &in, SeedStag
                     long long *h_prof = prof ? reinterpret_cast<long long *>(h_ids + ((2 * (size_t)nj + 1) & ~(size_t)1)) : nullptr;
                     std::copy(gids.begin(), gids.end(), h_ids);
                     std::fill(h_st, h_st + nj, 1);
-                    int *d_ids = dev<int>(S.replay_ids, nj);
+                    int *d_ids = S.replay_ids.ensure_n<int>(nj);
                     copy_from_host(d_ids, h_ids, sizeof(int) * nj, s);
-                    launch_gpu_replays(d_ids, nj, (int)maxw, d_off, d_fg, d_rec, hr, h_st, dev<int>(S.replay_order, nf),
+                    launch_gpu_replays(d_ids, nj, (int)maxw, d_off, d_fg, d_rec, hr, h_st, S.replay_order.ensure_n<int>(nf),
                                        g, d_poly, np, static_cast<float>(in.cluster_min_length), s, h_prof);
                     S.dedup.sev.sync(s);
                     tr.mark("replays_gpu");
@@ -977,7 +975,7 @@ void run_cluster_seed_stage(ClusterSeedState &S, const SeedStageIn &in, SeedStag
     // (the two small ones in one launch) and one kernel concatenates them: two host waits in all
     DedupScratch &scr = S.dedup;
     const int nr = (int)rows.size();
-    RowDev *d_rows = dev<RowDev>(S.row_idx, nr);
+    RowDev *d_rows = S.row_idx.ensure_n<RowDev>(nr);
     {
         RowDev *hr = static_cast<RowDev *>(S.h_up_rows.ensure(sizeof(RowDev) * (size_t)nr));
         std::copy(rows.begin(), rows.end(), hr);
@@ -985,11 +983,11 @@ void run_cluster_seed_stage(ClusterSeedState &S, const SeedStageIn &in, SeedStag
     }
     const int nslots = rows.back().slot0 + 3 * rows.back().k;
     const size_t ncand = (size_t)nslots + 8 * (size_t)nr;
-    double2 *d_cand = dev<double2>(S.cand_xy, ncand), *d_rcand = d_cand + nslots, *d_ecand = d_rcand + 6 * nr;
-    int *d_ok = dev<int>(S.cand_ok, ncand), *d_rok = d_ok + nslots, *d_eok = d_rok + 6 * nr;
-    double2 *d_vout = dev<double2>(S.cand_kept, ncand), *d_rout = d_vout + nslots, *d_eout = d_rout + 6 * nr;
-    double2 *d_seeds = dev<double2>(S.seed_out, ncand);
-    int *d_cnt = dev<int>(S.misc, 8);   // kept counts: virtual, ray, endpoint
+    double2 *d_cand = S.cand_xy.ensure_n<double2>(ncand), *d_rcand = d_cand + nslots, *d_ecand = d_rcand + 6 * nr;
+    int *d_ok = S.cand_ok.ensure_n<int>(ncand), *d_rok = d_ok + nslots, *d_eok = d_rok + 6 * nr;
+    double2 *d_vout = S.cand_kept.ensure_n<double2>(ncand), *d_rout = d_vout + nslots, *d_eout = d_rout + 6 * nr;
+    double2 *d_seeds = S.seed_out.ensure_n<double2>(ncand);
+    int *d_cnt = S.misc.ensure_n<int>(8);   // kept counts: virtual, ray, endpoint
     const double hx0 = g.minx - 50.0, hx1 = g.maxx + 50.0, hy0 = g.miny - 50.0, hy1 = g.maxy + 50.0;
     RayAngles ang{};
     const double degs[3] = {0.0, -90.0, 90.0};
@@ -1002,7 +1000,7 @@ void run_cluster_seed_stage(ClusterSeedState &S, const SeedStageIn &in, SeedStag
         std::vector<double> t;
         for (double cur = 1.0;; cur += 0.1) { t.push_back(cur); if (!(cur <= g.amax)) break; }
         S.n_cur_tab = (int)t.size();
-        double *d = dev<double>(S.cur_tab, t.size());
+        double *d = S.cur_tab.ensure_n<double>(t.size());
         AOS_HIP(hipMemcpyAsync(d, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, s));
         S.dedup.sev.sync(s);
         tr.mark("curtab");

@@ -29,7 +29,6 @@
 
 namespace aos {
 
-static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 HashG make_hash(double minx, double maxx, double miny, double maxy, double cell) {
     HashG h{};
@@ -266,16 +265,15 @@ __global__ void k_ci_scatter(const double2 *p, const int *rank, int n, HashG h, 
     items[start[cy * h.nx + cx] + r] = i;
 }
 
-template <class T> static T *dev(DevBuf &b, size_t n) { return static_cast<T *>(b.ensure(sizeof(T) * std::max<size_t>(n, 1))); }
 
 CellIdx cell_index_build(CellScratch &S, const double2 *p, const int *ok, int n, const HashG &h, hipStream_t s,
                          const int *n_dev) {
     const long long nb = (long long)h.nx * h.ny;
     if (nb >= INT_MAX) throw std::runtime_error("cell index: too many buckets");
     const size_t cap0 = S.cnt.cap;
-    int *cnt = dev<int>(S.cnt, (size_t)nb + 1);
+    int *cnt = S.cnt.ensure_n<int>((size_t)nb + 1);
     if (S.dirty || S.cnt.cap != cap0) AOS_HIP(hipMemsetAsync(cnt, 0, S.cnt.cap, s));
-    int *start = dev<int>(S.start, (size_t)nb + 1), *items = dev<int>(S.items, n), *rank = dev<int>(S.rank, n);
+    int *start = S.start.ensure_n<int>((size_t)nb + 1), *items = S.items.ensure_n<int>(n), *rank = S.rank.ensure_n<int>(n);
     S.dirty = true;
     if (n > 0) k_ci_count<<<cdiv(n, 256), 256, 0, s>>>(p, ok, n, n_dev, h, cnt, rank);
     scan_1p(S.lb, cnt, start, (int)nb, true, s);   // (leaves the counts zero for the next build)
@@ -518,7 +516,7 @@ void greedy_dedup_async(DedupScratch &S, const double2 *cand, const int *ok, int
     S.cells.lb.ext_err = dedup_err(S, s);   // (one error word for all of S's launches)
     S.ci = cell_index_build(S.cells, cand, ok, n, h, s);
     const size_t cap0 = S.state.cap;
-    int *state = dev<int>(S.state, n);
+    int *state = S.state.ensure_n<int>(n);
     if (S.state.cap != cap0) AOS_HIP(hipMemsetAsync(state, 0, S.state.cap, s));   // (epoch 0: undecided)
     if (++S.epoch >= (1u << 29)) {
         S.epoch = 1;

@@ -14,7 +14,6 @@
 
 namespace aos {
 
-static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // (a1-a4, ROR + clip + raster: ror.hip)
 

@@ -39,8 +39,6 @@ constexpr double kLabelRange = 1.0;    // ... over the grid +- 1 m
 constexpr int kPairCapMin = 1024;      // g6: the pair lists hold at least this many pairs
 constexpr double kPairMin = 1e-6, kPairMax = 0.5;   // g6 pairs: kPairMin < |bp_i - bp_j| <= kPairMax (gvd:861-894)
 
-static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
-template <class T> static T *dev(DevBuf &b, size_t n) { return static_cast<T *>(b.ensure(sizeof(T) * std::max<size_t>(n, 1))); }
 
 struct GridG {
     double ox, oy, res;             // info.origin, (double)info.resolution
@@ -760,8 +758,8 @@ static int facets_count(FacetBufs &F, const Subdiv2D &sd, Subdiv2D::Raw &R, int 
     const float2 *d_vp = reinterpret_cast<const float2 *>(d + bq);
     F.vf = reinterpret_cast<int *>(d + bq + bv);
     F.vt = reinterpret_cast<int *>(d + bq + bv + bi);
-    float2 *d_face = dev<float2>(F.face, 2 * (size_t)R.n_rec);
-    int *d_cnt = dev<int>(F.cnt, R.n_vtx + 1), *d_off = dev<int>(F.off, R.n_vtx + 2);   // off[n_vtx + 1]: walk error
+    float2 *d_face = F.face.ensure_n<float2>(2 * (size_t)R.n_rec);
+    int *d_cnt = F.cnt.ensure_n<int>(R.n_vtx + 1), *d_off = F.off.ensure_n<int>(R.n_vtx + 2);   // off[n_vtx + 1]: walk error
     k_vor_faces<<<cdiv(2 * R.n_rec, 256), 256, 0, s>>>(F.qe, R.n_rec, d_vp, d_face, d_off + R.n_vtx + 1);
     {
         const int blocks = cdiv((long long)R.n_vtx + 1, 256);
@@ -825,7 +823,7 @@ static GridG make_grid(const aos_grid_info &info) {
 static int merge_seeds(GvdState &G, GvdScratch &S, const GridG &g, const GvdStageIn &in, int *h_sc, hipStream_t s,
                        HostTrace &tr, std::vector<double> &merged) {
     const int n = in.n_seeds;
-    double2 *d_raw = dev<double2>(S.raw, n);
+    double2 *d_raw = S.raw.ensure_n<double2>(n);
     // seeds in and merged seeds out through the state's pinned buffer (a pageable copy is staged by the
     // runtime and, measured on the streaming map, could stall ~20 ms behind unrelated copy traffic)
     double *h_seeds = static_cast<double *>(G.h_seeds.ensure(sizeof(double2) * (size_t)n));
@@ -834,9 +832,9 @@ static int merge_seeds(GvdState &G, GvdScratch &S, const GridG &g, const GvdStag
     tr.mark("h2d");
     const HashG hm = make_hash_n(g.minx - kMergeRange, g.maxx + kMergeRange, g.miny - kMergeRange, g.maxy + kMergeRange,
                                  kMergeRadius, n);
-    double2 *d_merged = dev<double2>(S.merged, n);
-    int *d_leaders = dev<int>(S.leaders, n), *d_owner = dev<int>(S.owner, n);
-    int *d_cnt = dev<int>(S.misc, 8);
+    double2 *d_merged = S.merged.ensure_n<double2>(n);
+    int *d_leaders = S.leaders.ensure_n<int>(n), *d_owner = S.owner.ensure_n<int>(n);
+    int *d_cnt = S.misc.ensure_n<int>(8);
     // leaders (the kept seeds) -> d_merged, overwritten in leader order by their means
     greedy_dedup_async(G.dedup, d_raw, nullptr, n, kConflictLessEq, kMergeRadius, hm, d_merged, d_leaders, d_owner, d_cnt, s);
     // (the means and the count come back from the same launch: one host wait)
@@ -867,7 +865,7 @@ static int voronoi_edges(GvdState &G, GvdScratch &S, const GridG &g, const std::
     Subdiv2D::Raw R{};
     const int ne = facets_count(S.fb, G.subdiv, R, h_sc, s, G.sev);
     tr.mark("facets");
-    d_occ = dev<double2>(S.occ, 2 * (size_t)std::max(ne, 1));   // (g5's candidates: the edge ends)
+    d_occ = S.occ.ensure_n<double2>(2 * (size_t)std::max(ne, 1));   // (g5's candidates: the edge ends)
     if (ne) facets_emit(S.fb, R, nullptr, s, d_occ);
     return ne;
 }
@@ -914,30 +912,30 @@ static void graph_begin(GvdState &G, GvdScratch &S, GraphFrame &F, const double 
     const GridG &g = F.g;
     const int no = F.no, nj = F.nj;
     const HashG h5 = make_hash_n(g.minx - kBpRange, g.maxx + kBpRange, g.miny - kBpRange, g.maxy + kBpRange, kBpCell, no);
-    F.bp = dev<double2>(S.bp, no);
-    F.pos_of = dev<int>(S.pos_of, no);
-    int *d_sc = dev<int>(S.misc, 16);   // [0] M
+    F.bp = S.bp.ensure_n<double2>(no);
+    F.pos_of = S.pos_of.ensure_n<int>(no);
+    int *d_sc = S.misc.ensure_n<int>(16);   // [0] M
     greedy_dedup_async(G.dedup, F.occ, nullptr, no, kConflictKeyOrSq, kBpThr * kBpThr, h5, F.bp, nullptr, nullptr, d_sc, s,
                        F.pos_of);
     F.cio = G.dedup.ci;
     F.M = d_sc;
     if (count_evals) {   // (aos_params.gvd_count_evals)
-        F.evals = dev<unsigned long long>(S.evals, 8);
+        F.evals = S.evals.ensure_n<unsigned long long>(8);
         AOS_HIP(hipMemsetAsync(F.evals, 0, 8 * sizeof(unsigned long long), s));
     }
-    int *d_pcount = dev<int>(S.pcount, no);
-    F.poff = dev<int>(S.poff, no + 1);
+    int *d_pcount = S.pcount.ensure_n<int>(no);
+    F.poff = S.poff.ensure_n<int>(no + 1);
     k_pairs_count<<<cdiv(no, 256), 256, 0, s>>>(F.bp, no, F.M, F.cio, F.pos_of, F.occ, d_pcount, F.evals);
     scan_1p(S.lb, d_pcount, F.poff, no, false, s);
     jobs = label_jobs(rows_info, F.nrows);
-    F.jobs = dev<LabelRow>(S.jobs, nj);
+    F.jobs = S.jobs.ensure_n<LabelRow>(nj);
     if (nj) AOS_HIP(hipMemcpyAsync(F.jobs, jobs.data(), sizeof(LabelRow) * nj, hipMemcpyHostToDevice, s));
-    F.lp = dev<double2>(S.lpts, nj);
-    F.lv = dev<int>(S.lval, nj);
-    F.nodes = dev<double2>(S.nodes, no);
-    F.in = dev<int>(S.inside, no); F.ipos = dev<int>(S.ipos, no + 1);
-    F.mask = dev<int>(S.lmask, no); F.cidx = dev<int>(S.lcidx, no); F.lcnt = dev<int>(S.lcount, no);
-    F.loff = dev<int>(S.loff, no + 1);
+    F.lp = S.lpts.ensure_n<double2>(nj);
+    F.lv = S.lval.ensure_n<int>(nj);
+    F.nodes = S.nodes.ensure_n<double2>(no);
+    F.in = S.inside.ensure_n<int>(no); F.ipos = S.ipos.ensure_n<int>(no + 1);
+    F.mask = S.lmask.ensure_n<int>(no); F.cidx = S.lcidx.ensure_n<int>(no); F.lcnt = S.lcount.ensure_n<int>(no);
+    F.loff = S.loff.ensure_n<int>(no + 1);
 }
 
 // ---- one attempt of g5's nearest points to g9's counts with pair lists of capacity cap; returns the frame's sizes
@@ -946,16 +944,16 @@ static GraphSizes graph_attempt(GvdState &G, GvdScratch &S, GraphFrame &F, int c
                                 hipStream_t s) {
     const GridG &g = F.g;
     const int ne = F.ne, no = F.no, nj = F.nj, ncap = ne + cap;
-    int2 *d_ft = dev<int2>(S.ft, ncap);
+    int2 *d_ft = S.ft.ensure_n<int2>(ncap);
     // (round 5 measured k_nearest on a second stream beside the pair count, scan and lists: no gain, r05l)
     k_nearest<<<cdiv(no, 256), 256, 0, s>>>(F.occ, no, F.cio, F.pos_of, F.bp, F.M, reinterpret_cast<int *>(d_ft), ev_k);
     k_pairs<<<cdiv(no, 256), 256, 0, s>>>(F.bp, no, F.M, F.cio, F.pos_of, F.occ, F.poff, d_ft + ne, cap, ev_k);
-    int *d_pass = dev<int>(S.pass, ncap), *d_grank = dev<int>(S.grank, ncap), *d_sel = dev<int>(S.selected, ncap);
+    int *d_pass = S.pass.ensure_n<int>(ncap), *d_grank = S.grank.ensure_n<int>(ncap), *d_sel = S.selected.ensure_n<int>(ncap);
     const size_t gc0 = S.gcnt.cap;
-    int *d_gcnt = dev<int>(S.gcnt, no);
+    int *d_gcnt = S.gcnt.ensure_n<int>(no);
     if (S.gcnt.cap != gc0 || S.gcnt_dirty) AOS_HIP(hipMemsetAsync(d_gcnt, 0, S.gcnt.cap, s));
     S.gcnt_dirty = true;
-    int *d_goff = dev<int>(S.goff, no + 1), *d_glist = dev<int>(S.glist, ncap);
+    int *d_goff = S.goff.ensure_n<int>(no + 1), *d_glist = S.glist.ensure_n<int>(ncap);
     k_occupancy<<<cdiv(ncap, kOccTB), kOccTB, 0, s>>>(d_ft, F.poff, no, ne, cap, F.bp, F.sk, g, d_pass, d_gcnt, d_grank, ev_k);
     scan_1p(S.lb, d_gcnt, d_goff, no, true, s);   // (leaves the group counts zero)
     S.gcnt_dirty = false;
@@ -965,11 +963,11 @@ static GraphSizes graph_attempt(GvdState &G, GvdScratch &S, GraphFrame &F, int c
     // ---- g7 filter
     k_inside<<<cdiv(no, 256), 256, 0, s>>>(F.bp, no, F.M, g, F.in);
     scan_1p(S.lb, F.in, F.ipos, no, false, s);
-    int *d_keep = dev<int>(S.keep, ncap), *d_kpos = dev<int>(S.kpos, ncap + 1);
+    int *d_keep = S.keep.ensure_n<int>(ncap), *d_kpos = S.kpos.ensure_n<int>(ncap + 1);
     k_edge_keep<<<cdiv(std::max(ncap, no), 256), 256, 0, s>>>(d_sel, d_ft, ncap, F.in, F.ipos, d_keep, F.bp, no, F.nodes);
     scan_1p(S.lb, d_keep, d_kpos, ncap, false, s);
-    F.edges = dev<int>(S.edges, 2 * (size_t)ncap);
-    F.lens = dev<float>(S.lens, ncap);
+    F.edges = S.edges.ensure_n<int>(2 * (size_t)ncap);
+    F.lens = S.lens.ensure_n<float>(ncap);
     k_edge_emit<<<cdiv(ncap, 256), 256, 0, s>>>(d_keep, d_kpos, d_ft, ncap, F.ipos, F.nodes, F.edges, F.lens);
     const int *d_Mn = F.ipos + no;
 
@@ -1004,8 +1002,8 @@ static int gather_outputs(GvdState &G, GvdScratch &S, const GraphFrame &F, const
                           hipEvent_t ev_out, HostTrace &tr) {
     const int Mn = z.Mn, Ne = z.Ne, n_entries = z.n_entries;
     const int nj_out = Mn > 0 ? F.nj : 0;   // (no nodes: no label jobs, gvd:485-556 finds nothing to label)
-    int *d_lcl = dev<int>(S.lcl, n_entries);
-    int *d_lty = dev<int>(S.lty, n_entries);
+    int *d_lcl = S.lcl.ensure_n<int>(n_entries);
+    int *d_lty = S.lty.ensure_n<int>(n_entries);
     if (n_entries)
         k_node_labels_fill<<<cdiv(Mn, 256), 256, 0, s>>>(F.nodes, Mn, F.lp, F.lv, F.nrows, S.cq, F.loff, d_lcl, d_lty);
 

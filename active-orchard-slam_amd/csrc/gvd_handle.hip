@@ -201,6 +201,40 @@ void aos_ctx::gvd_view_settle() {
     if (ok && (cur_lane != l || !have_gvd)) lane_apply(l);
 }
 
+// The planner calls' graph: the caller's, or the current result's (the caller has settled which one that is), every
+// array of it, with load_graph's cache key; markers_wait first, as every reader of gs() on the caller's thread does.
+aos_ctx::PlanGraph aos_ctx::plan_graph(const aos_path_graph *graph) {
+    if (graph) return {*graph, nullptr, 0};
+    if (!have_gvd) throw std::runtime_error("no GVD graph on this handle");
+    GvdState &G = gs();
+    markers_wait(G, false);
+    aos_path_graph own{};
+    own.num_nodes = (int32_t)G.labels.size(); own.nodes_xy = G.nodes_xy.data();
+    own.node_labels = G.labels.data(); own.node_cluster_indices = G.cluster_idx.data();
+    own.node_label_counts = G.label_counts.data();
+    own.n_label_entries = (int32_t)G.label_clusters.size();
+    own.node_label_clusters = G.label_clusters.data(); own.node_label_types = G.label_types.data();
+    own.num_edges = (int32_t)G.lengths.size(); own.edges = G.edges_out.data(); own.edge_lengths = G.lengths.data();
+    return {own, &G, gvd_gen};
+}
+
+// The planner calls' grid on the device: the caller's device pointer as it is, the caller's host grid copied into
+// staging on the handle's stream (never null: staging holds a byte at least), or the skeleton of the current GVD
+// result while it is still the one that call used.
+aos_ctx::PlanGrid aos_ctx::plan_grid(const int8_t *grid, int on_device, const aos_grid_info *info, DevBuf &staging) {
+    if (grid) {
+        if (on_device) return {grid, *info};
+        const size_t C = (size_t)info->width * info->height;
+        int8_t *d = staging.ensure_n<int8_t>(C);
+        if (C) AOS_HIP(hipMemcpyAsync(d, grid, C, hipMemcpyHostToDevice, stream));
+        return {d, *info};
+    }
+    if (!have_gvd) throw std::runtime_error("no grid given and no GVD call on this handle");
+    if (gvd_from_frame && gvd_frame_gen != frame_gen)
+        throw std::runtime_error("the GVD graph's skeleton was replaced by a later seed-gen frame; pass the grid");
+    return {gvd_skel, gvd_info};
+}
+
 // A synchronous GVD call (or the handle's release) supersedes every job in flight.
 void aos_ctx::gvd_async_drop() {
     gvd_lanes_ensure();

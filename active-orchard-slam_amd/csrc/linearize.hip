@@ -67,8 +67,6 @@ struct LinState {
     lin::Result res;
 };
 
-void free_lin_state(void *p) { delete static_cast<LinState *>(p); }
-
 namespace {
 
 // findBestSplitPoint over [s, e] of the n uploaded poses, e > s + 1: one launch and one host wait
@@ -97,23 +95,20 @@ int gpu_search(LinState &S, int n, int s, int e, hipStream_t stream) {
 using namespace aos;
 
 extern "C" int aos_path_linearize(aos_ctx *c, const double *poses, int32_t n_poses, aos_linear_path_out *out) {
-    if (!c || !out) { set_error("aos_path_linearize: null argument"); return AOS_E_INVALID; }
-    if (n_poses < 0) { set_error("aos_path_linearize: negative pose count"); return AOS_E_INVALID; }
-    if (!poses && n_poses > 0) { set_error("aos_path_linearize: null poses behind a count above 0"); return AOS_E_INVALID; }
-    if (n_poses > lin::kMaxPosesIn) { set_error("aos_path_linearize: more than 65536 poses"); return AOS_E_INVALID; }
-    try {
+    if (!c || !out) return fail(AOS_E_INVALID, "aos_path_linearize: null argument");
+    if (n_poses < 0) return fail(AOS_E_INVALID, "aos_path_linearize: negative pose count");
+    if (!poses && n_poses > 0) return fail(AOS_E_INVALID, "aos_path_linearize: null poses behind a count above 0");
+    if (n_poses > lin::kMaxPosesIn) return fail(AOS_E_INVALID, "aos_path_linearize: more than 65536 poses");
+    return guarded("linearize", nullptr, [&]() -> int {
         const auto t0 = std::chrono::steady_clock::now();
         DeviceScope dev_scope(c->device);
         int n = n_poses;
         if (!poses) {   // the fused form: the last aos_path_plan's poses (its arrays are only read)
-            if (!path_last_poses(c->path_state, &poses, &n)) {
-                set_error("aos_path_linearize: no aos_path_plan on this handle yet");
-                return AOS_E_STATE;
-            }
-            if (n > lin::kMaxPosesIn) { set_error("aos_path_linearize: more than 65536 poses"); return AOS_E_INVALID; }
+            if (!path_last_poses(c->path_state, &poses, &n))
+                return fail(AOS_E_STATE, "aos_path_linearize: no aos_path_plan on this handle yet");
+            if (n > lin::kMaxPosesIn) return fail(AOS_E_INVALID, "aos_path_linearize: more than 65536 poses");
         }
-        if (!c->lin_state) c->lin_state = new LinState();
-        LinState &S = *static_cast<LinState *>(c->lin_state);
+        LinState &S = c->lin_state.get<LinState>();
         bool uploaded = false;
         const lin::SplitSearch search = [&](int s, int e) {
             if (!uploaded) {   // the positions, once per call
@@ -136,18 +131,5 @@ extern "C" int aos_path_linearize(aos_ctx *c, const double *poses, int32_t n_pos
         out->n_split_searches = S.res.n_split_searches;
         out->ms_linearize = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return AOS_OK;
-    } catch (const HipError &e) {
-        set_error(std::string("HIP error ") + hipGetErrorString(e.e) + " at linearize line " + std::to_string(e.line) + ": " +
-                  e.what);
-        return AOS_E_HIP;
-    } catch (const std::bad_alloc &) {
-        set_error("out of host memory");
-        return AOS_E_NOMEM;
-    } catch (const std::invalid_argument &e) {
-        set_error(std::string("invalid argument: ") + e.what());
-        return AOS_E_INVALID;
-    } catch (const std::exception &e) {
-        set_error(std::string("error: ") + e.what());
-        return AOS_E_STATE;
-    }
+    });
 }

@@ -142,10 +142,8 @@ struct PathState {
     bool planned = false;   // a plan has filled the outputs (aos_path_linearize's fused form reads poses)
 };
 
-void free_path_state(void *p) { delete static_cast<PathState *>(p); }
-
-bool path_last_poses(const void *path_state, const double **poses, int *n) {
-    const PathState *S = static_cast<const PathState *>(path_state);
+bool path_last_poses(const OwnedState &path_state, const double **poses, int *n) {
+    const PathState *S = path_state.peek<PathState>();
     if (!S || !S->planned) return false;
     *poses = S->poses.data();
     *n = (int)(S->poses.size() / 4);
@@ -509,48 +507,12 @@ void aos_ctx::run_path_plan(const aos_path_graph *graph, const int8_t *skeleton,
                             const aos_grid_info *info, const aos_path_query &q, aos_path_out &out) {
     const auto t0 = std::chrono::steady_clock::now();
     gvd_view_settle();
-    if (!path_state) path_state = new PathState();
-    PathState &S = *static_cast<PathState *>(path_state);
-    // the graph
-    aos_path_graph own{};
-    const void *key = nullptr;
-    uint64_t gen = 0;
-    if (!graph) {
-        if (!have_gvd) throw std::runtime_error("aos_path_plan: no GVD graph on this handle");
-        GvdState &gs = this->gs();
-        markers_wait(gs, false);
-        own.num_nodes = (int32_t)gs.labels.size(); own.nodes_xy = gs.nodes_xy.data();
-        own.node_labels = gs.labels.data(); own.node_cluster_indices = gs.cluster_idx.data();
-        own.node_label_counts = gs.label_counts.data();
-        own.n_label_entries = (int32_t)gs.label_clusters.size();
-        own.node_label_clusters = gs.label_clusters.data(); own.node_label_types = gs.label_types.data();
-        own.num_edges = (int32_t)gs.lengths.size(); own.edges = gs.edges_out.data(); own.edge_lengths = gs.lengths.data();
-        graph = &own;
-        key = &gs;
-        gen = gvd_gen;
-    }
-    // the skeleton (device)
-    const int8_t *d_grid = nullptr;
-    aos_grid_info gi{};
-    if (skeleton) {
-        gi = *info;
-        const size_t C = (size_t)gi.width * gi.height;
-        if (skeleton_on_device) d_grid = skeleton;
-        else {
-            int8_t *d = static_cast<int8_t *>(S.d_grid.ensure(std::max<size_t>(C, 1)));
-            if (C) AOS_HIP(hipMemcpyAsync(d, skeleton, C, hipMemcpyHostToDevice, stream));
-            d_grid = d;
-        }
-    } else {
-        if (!have_gvd) throw std::runtime_error("aos_path_plan: no skeleton given and no GVD call on this handle");
-        if (gvd_from_frame && gvd_frame_gen != frame_gen)
-            throw std::runtime_error("aos_path_plan: the GVD graph's skeleton was replaced by a later seed-gen frame; pass it");
-        d_grid = gvd_skel;
-        gi = gvd_info;
-    }
-    load_graph(S, *graph, key, gen, stream);
+    PathState &S = path_state.get<PathState>();
+    const PlanGraph pg = plan_graph(graph);
+    const PlanGrid grid = plan_grid(skeleton, skeleton_on_device, info, S.d_grid);
+    load_graph(S, pg.g, pg.key, pg.gen, stream);
 
-    Planner pl(S, *graph, stream, d_grid, gi);
+    Planner pl(S, pg.g, stream, grid.d_grid, grid.info);
     pl.initial_reached = q.initial_waypoint_reached != 0;
     pl.initial = {q.initial_waypoint_xy[0], q.initial_waypoint_xy[1]};
     pl.target = q.target_waypoint_index;

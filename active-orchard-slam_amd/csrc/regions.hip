@@ -34,34 +34,20 @@
 #include "cluster_geom.h"
 #include "cluster_seed.h"
 #include "dev_prims.h"
+#include "field_passes.h"
 #include "regions.h"
 
 namespace aos {
 
-// (tests/regions_scenes.py names these sizes: its sweeps run +-1 around each)
-constexpr int kRgBand = 64;     // rows per band of the column pass (clearance.hip's kClrBand: the shared band words)
-constexpr int kRgTB = 256;      // threads per workgroup, every kernel here
-constexpr int kRgBlock = 64;    // columns per block minimum of the row pass (a wave's cells)
-constexpr unsigned kRgAbsNone = 0xFFFF;   // |offset| of a column without a site
+// (the band, workgroup and block sizes: field_passes.h, one set with clearance.hip, whose band words this file reads)
 
 // the words of the device statistics block (RegionsState::stats)
 enum { kStSites = 0 /* 64 bits */, kStMaxD2 = 2, kStRegions = 3, kStRidge = 4 /* 64 bits */, kStOccupied = 6 /* 64 bits */,
        kStWords = 8 };
 
-static inline int rg_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
-
-__device__ __forceinline__ unsigned rg_wave_min(unsigned v) {
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, o));
-    return v;
-}
-__device__ __forceinline__ unsigned rg_wave_max(unsigned v) {
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o));
-    return v;
-}
-
 // fg[y * WW + w]: bit b = cell (64 w + b, y) is occupied; cnt: its popcount. grid (cdiv(W, 256), H)
-__global__ void __launch_bounds__(kRgTB) k_rg_pack(const int8_t *grid, int W, int WW, uint64_t *fg, int *cnt) {
-    const int x = blockIdx.x * kRgTB + threadIdx.x, y = blockIdx.y;
+__global__ void __launch_bounds__(kFieldTB) k_rg_pack(const int8_t *grid, int W, int WW, uint64_t *fg, int *cnt) {
+    const int x = blockIdx.x * kFieldTB + threadIdx.x, y = blockIdx.y;
     const bool occ = x < W && grid[(size_t)y * W + x] == 100;
     const unsigned long long m = __ballot(occ);
     if ((threadIdx.x & 63) == 0 && x < W) {
@@ -71,16 +57,16 @@ __global__ void __launch_bounds__(kRgTB) k_rg_pack(const int8_t *grid, int W, in
 }
 
 // size[root] = the component's cells (size zeroed before)
-__global__ void __launch_bounds__(kRgTB) k_rg_size(const int *parent, int nf, int *size) {
-    const int i = blockIdx.x * kRgTB + threadIdx.x;
+__global__ void __launch_bounds__(kFieldTB) k_rg_size(const int *parent, int nf, int *size) {
+    const int i = blockIdx.x * kFieldTB + threadIdx.x;
     if (i < nf) atomicAdd(&size[parent[i]], 1);
 }
 
 // The kept components' cells become sites: sb[cell] = 100 (sb zeroed before), lab[cell] = the root's cell.
 // st[kStRegions] += the kept components.
-__global__ void __launch_bounds__(kRgTB) k_rg_sites(const int *list, const int *parent, const int *size, int nf, int min_cells,
-                                                   int8_t *sb, int32_t *lab, unsigned *st) {
-    const int i = blockIdx.x * kRgTB + threadIdx.x;
+__global__ void __launch_bounds__(kFieldTB) k_rg_sites(const int *list, const int *parent, const int *size, int nf, int min_cells,
+                                                       int8_t *sb, int32_t *lab, unsigned *st) {
+    const int i = blockIdx.x * kFieldTB + threadIdx.x;
     bool kept_root = false;
     if (i < nf) {
         const int r = parent[i];
@@ -96,9 +82,9 @@ __global__ void __launch_bounds__(kRgTB) k_rg_sites(const int *list, const int *
 }
 
 // Caller labels: sb[c] = 100 iff the cell is occupied and its label >= 0. st[kStOccupied] += the occupied cells.
-__global__ void __launch_bounds__(kRgTB) k_rg_label_sites(const int8_t *grid, const int32_t *labels, size_t C, int8_t *sb,
-                                                         unsigned *st) {
-    const size_t c = (size_t)blockIdx.x * kRgTB + threadIdx.x;
+__global__ void __launch_bounds__(kFieldTB) k_rg_label_sites(const int8_t *grid, const int32_t *labels, size_t C, int8_t *sb,
+                                                             unsigned *st) {
+    const size_t c = (size_t)blockIdx.x * kFieldTB + threadIdx.x;
     bool occ = false;
     if (c < C) {
         occ = grid[c] == 100;
@@ -111,88 +97,54 @@ __global__ void __launch_bounds__(kRgTB) k_rg_label_sites(const int8_t *grid, co
 
 // off[y * W + x] = (the row of the column's nearest site) - y, the smaller row at equal distance; kOffNone without
 // one. masks / up / down: k_clr_bands' and k_clr_carry's. grid (cdiv(W, 256), bands)
-__global__ void __launch_bounds__(kRgTB) k_rg_cols(const unsigned long long *masks, const int *up, const int *down, int W,
-                                                  int H, int16_t *off) {
-    const int x = blockIdx.x * kRgTB + threadIdx.x, b = blockIdx.y;
+__global__ void __launch_bounds__(kFieldTB) k_rg_cols(const unsigned long long *masks, const int *up, const int *down, int W,
+                                                      int H, int16_t *off) {
+    const int x = blockIdx.x * kFieldTB + threadIdx.x, b = blockIdx.y;
     if (x >= W) return;
     const unsigned long long m = masks[(size_t)b * W + x];
     const int cu = up[(size_t)b * W + x], cd = down[(size_t)b * W + x];
-    const int y0 = b * kRgBand, rows = min(kRgBand, H - y0);
+    const int y0 = b * kFieldBand, rows = min(kFieldBand, H - y0);
     for (int r = 0; r < rows; ++r) {
         const int y = y0 + r;
-        const unsigned long long lo = m & (~0ull >> (63 - r)), hi = m & (~0ull << r);
-        const int above = lo ? y0 + 63 - __clzll((long long)lo) : cu;
-        const int below = hi ? y0 + __ffsll((long long)hi) - 1 : cd;
+        const NearestRows n = band_nearest_rows(m, cu, cd, y0, r);
         int o = rgn::kOffNone;
-        if (above >= 0) o = above - y;
-        if (below >= 0 && (above < 0 || below - y < y - above)) o = below - y;
+        if (n.above >= 0) o = n.above - y;
+        if (n.below >= 0 && (n.above < 0 || n.below - y < y - n.above)) o = n.below - y;
         off[(size_t)y * W + x] = (int16_t)o;
     }
 }
 
+// field_row_pass on the row offsets: a candidate is (d2, the site's linear index) and the least pair wins, so the
+// prunes admit ties (an equal d2 may still win by its index)
+struct RgRowPass {
+    typedef int16_t Stored;
+    static constexpr Stored kNone = rgn::kOffNone;
+    static constexpr bool kTies = true;
+    struct Cand { unsigned d2 = clr::kNone, idx = rgn::kSiteNone; };
+    static __device__ __forceinline__ unsigned mag(int o) { return o == rgn::kOffNone ? kFieldMagNone : (unsigned)abs(o); }
+    static __device__ __forceinline__ void update(Cand &c, int o, int x, int xp, int y, int W) {
+        if (o == rgn::kOffNone) return;
+        const int dx = x - xp;
+        const unsigned v = (unsigned)(dx * dx + o * o);
+        if (v > c.d2) return;
+        const unsigned idx = (unsigned)(y + o) * (unsigned)W + (unsigned)xp;
+        if (v < c.d2 || idx < c.idx) { c.d2 = v; c.idx = idx; }
+    }
+};
+
 // One workgroup per row. site[y * W + x] = the linear index of the site with the least (d2, index); *max_d2: the
 // maximum d2 (atomicMax per wave; kNone where no cell has a site).
-__global__ void __launch_bounds__(kRgTB) k_rg_rows(const int16_t *off, int W, uint32_t *site, unsigned *max_d2) {
-    __shared__ int16_t os[clr::kMaxDim];
-    __shared__ uint16_t bmin[clr::kMaxDim / kRgBlock];
-    const int y = blockIdx.x, tid = threadIdx.x;
-    const int16_t *orow = off + (size_t)y * W;
-    for (int x0 = 0; x0 < W; x0 += kRgTB) {   // (uniform bounds: every lane takes part in the wave minimum)
-        const int x = x0 + tid;
-        const int o = x < W ? orow[x] : rgn::kOffNone;
-        if (x < W) os[x] = (int16_t)o;
-        const unsigned wm = rg_wave_min(o == rgn::kOffNone ? kRgAbsNone : (unsigned)abs(o));
-        if ((tid & 63) == 0 && x < W) bmin[x / kRgBlock] = (uint16_t)wm;
-    }
-    __syncthreads();
-    const int nblk = (W + kRgBlock - 1) / kRgBlock;
-    unsigned row_max = 0;
-    for (int x = tid; x < W; x += kRgTB) {
-        unsigned bd = clr::kNone, bi = rgn::kSiteNone;
-        auto scan = [&](int B) {
-            const int a = B * kRgBlock, e = min(W, a + kRgBlock);
-            for (int xp = a; xp < e; ++xp) {
-                const int o = os[xp];
-                if (o == rgn::kOffNone) continue;
-                const int dx = x - xp;
-                const unsigned v = (unsigned)(dx * dx + o * o);
-                if (v > bd) continue;
-                const unsigned idx = (unsigned)(y + o) * (unsigned)W + (unsigned)xp;
-                if (v < bd || idx < bi) { bd = v; bi = idx; }
-            }
-        };
-        const int bx = x / kRgBlock;
-        scan(bx);
-        for (int k = 1;; ++k) {
-            const int bl = bx - k, br = bx + k;
-            bool any = false;
-            if (bl >= 0) {
-                const unsigned db = (unsigned)(x - (bl * kRgBlock + kRgBlock - 1));
-                if (db * db <= bd) {   // (strict prunes: an equal d2 may still win by its index)
-                    any = true;
-                    const unsigned gm = bmin[bl];
-                    if (gm != kRgAbsNone && db * db + gm * gm <= bd) scan(bl);
-                }
-            }
-            if (br < nblk) {
-                const unsigned db = (unsigned)(br * kRgBlock - x);
-                if (db * db <= bd) {
-                    any = true;
-                    const unsigned gm = bmin[br];
-                    if (gm != kRgAbsNone && db * db + gm * gm <= bd) scan(br);
-                }
-            }
-            if (!any) break;
-        }
-        site[(size_t)y * W + x] = bi;
-        row_max = max(row_max, bd);
-    }
-    row_max = rg_wave_max(row_max);
-    if ((tid & 63) == 0) atomicMax(max_d2, row_max);
+__global__ void __launch_bounds__(kFieldTB) k_rg_rows(const int16_t *off, int W, uint32_t *site, unsigned *max_d2) {
+    const int y = blockIdx.x;
+    unsigned row_max = field_row_pass<RgRowPass>(off + (size_t)y * W, y, W, [&](int x, const RgRowPass::Cand &c) {
+        site[(size_t)y * W + x] = c.idx;
+    });
+    row_max = wave_max_u32(row_max);
+    if ((threadIdx.x & 63) == 0) atomicMax(max_d2, row_max);
 }
 
-__global__ void __launch_bounds__(kRgTB) k_rg_region(const uint32_t *site, const int32_t *lab, size_t C, int32_t *region) {
-    const size_t c = (size_t)blockIdx.x * kRgTB + threadIdx.x;
+__global__ void __launch_bounds__(kFieldTB) k_rg_region(const uint32_t *site, const int32_t *lab, size_t C, int32_t *region) {
+    const size_t c = (size_t)blockIdx.x * kFieldTB + threadIdx.x;
     if (c >= C) return;
     const uint32_t s = site[c];
     region[c] = s == rgn::kSiteNone ? rgn::kRegionNone : lab[s];
@@ -201,9 +153,9 @@ __global__ void __launch_bounds__(kRgTB) k_rg_region(const uint32_t *site, const
 // The pair rule seen from the cell that is marked: a cell that is no site cell is marked by its forward pairs (right,
 // down) whose regions differ, and by its backward pairs (left, up) whose regions differ and whose first cell is a
 // site cell. *n_ridge += the marked cells.
-__global__ void __launch_bounds__(kRgTB) k_rg_ridge(const uint32_t *site, const int32_t *region, int W, int H, int8_t *ridge,
-                                                   unsigned long long *n_ridge) {
-    const size_t C = (size_t)W * H, c = (size_t)blockIdx.x * kRgTB + threadIdx.x;
+__global__ void __launch_bounds__(kFieldTB) k_rg_ridge(const uint32_t *site, const int32_t *region, int W, int H, int8_t *ridge,
+                                                       unsigned long long *n_ridge) {
+    const size_t C = (size_t)W * H, c = (size_t)blockIdx.x * kFieldTB + threadIdx.x;
     bool mark = false;
     if (c < C) {
         const int y = (int)(c / W), x = (int)(c - (size_t)y * W);
@@ -223,11 +175,11 @@ __global__ void __launch_bounds__(kRgTB) k_rg_ridge(const uint32_t *site, const 
 
 // One thread per point; the outputs are pinned host memory, n words each. ridge_d2 nullable (every word kNone).
 // st (nullable): the statistics block, copied to h_stats by the first thread with *n_comp (nullable) behind it.
-__global__ void __launch_bounds__(kRgTB) k_rg_sample(clr::Grid g, const uint32_t *site, const int32_t *region,
-                                                    const uint32_t *ridge_d2, const double2 *pts, int n, uint32_t *o_site,
-                                                    int32_t *o_region, uint32_t *o_d2, uint32_t *o_rd2, const unsigned *st,
-                                                    const int *n_comp, uint32_t *h_stats) {
-    const int i = blockIdx.x * kRgTB + threadIdx.x;
+__global__ void __launch_bounds__(kFieldTB) k_rg_sample(clr::Grid g, const uint32_t *site, const int32_t *region,
+                                                        const uint32_t *ridge_d2, const double2 *pts, int n, uint32_t *o_site,
+                                                        int32_t *o_region, uint32_t *o_d2, uint32_t *o_rd2, const unsigned *st,
+                                                        const int *n_comp, uint32_t *h_stats) {
+    const int i = blockIdx.x * kFieldTB + threadIdx.x;
     if (i == 0 && st) {
         for (int k = 0; k < kStWords; ++k) h_stats[k] = st[k];
         h_stats[kStWords] = n_comp ? (uint32_t)*n_comp : 0u;
@@ -265,20 +217,13 @@ struct RegionsState {
     }
 };
 
-void free_regions_state(void *p) { delete static_cast<RegionsState *>(p); }
-
 namespace {
 
 RegionsState &regions_state(aos_ctx *c) {
-    if (!c->regions_state) c->regions_state = new RegionsState();
-    RegionsState &S = *static_cast<RegionsState *>(c->regions_state);
+    RegionsState &S = c->regions_state.get<RegionsState>();
     for (hipEvent_t &e : S.ev) if (!e) AOS_HIP(hipEventCreate(&e));
     return S;
 }
-
-template <class T> T *rg_dev(DevBuf &b, size_t n) { return static_cast<T *>(b.ensure(sizeof(T) * std::max<size_t>(n, 1))); }
-
-int fail(int code, const std::string &msg) { set_error(msg); return code; }
 
 // Sites and labels from the components: S.sb, S.lab, st[kStRegions]; returns the occupied count, *n_comp_dev = where
 // the component count lies on the device
@@ -286,13 +231,13 @@ int launch_components(RegionsState &S, const int8_t *d_grid, int W, int H, int m
                       hipStream_t s) {
     const size_t C = (size_t)W * H;
     GridC gc{};
-    gc.W = W; gc.H = H; gc.WW = rg_cdiv(W, 64);
+    gc.W = W; gc.H = H; gc.WW = cdiv(W, 64);
     const size_t Cw = (size_t)gc.WW * H;
-    uint64_t *fg = rg_dev<uint64_t>(S.fg, Cw);
-    int *cnt = rg_dev<int>(S.cnt, Cw), *off = rg_dev<int>(S.ccl.off, Cw + 1);
-    int8_t *sb = rg_dev<int8_t>(S.sb, C);
-    int32_t *lab = rg_dev<int32_t>(S.lab, C);
-    k_rg_pack<<<dim3(rg_cdiv(W, kRgTB), H), kRgTB, 0, s>>>(d_grid, W, gc.WW, fg, cnt);
+    uint64_t *fg = S.fg.ensure_n<uint64_t>(Cw);
+    int *cnt = S.cnt.ensure_n<int>(Cw), *off = S.ccl.off.ensure_n<int>(Cw + 1);
+    int8_t *sb = S.sb.ensure_n<int8_t>(C);
+    int32_t *lab = S.lab.ensure_n<int32_t>(C);
+    k_rg_pack<<<dim3(cdiv(W, kFieldTB), H), kFieldTB, 0, s>>>(d_grid, W, gc.WW, fg, cnt);
     AOS_HIP(hipGetLastError());
     scan_1p(S.ccl.lb, cnt, off, (int)Cw, false, s);
     AOS_HIP(hipMemsetAsync(sb, 0, C, s));
@@ -301,10 +246,10 @@ int launch_components(RegionsState &S, const int8_t *d_grid, int W, int H, int m
     if (err) throw std::runtime_error("a single-pass scan failed on the device");
     *n_comp_dev = S.ccl.rank_p + nf;
     if (nf > 0) {
-        int *size = rg_dev<int>(S.size, nf);
+        int *size = S.size.ensure_n<int>(nf);
         AOS_HIP(hipMemsetAsync(size, 0, sizeof(int) * (size_t)nf, s));
-        k_rg_size<<<rg_cdiv(nf, kRgTB), kRgTB, 0, s>>>(S.ccl.parent_p, nf, size);
-        k_rg_sites<<<rg_cdiv(nf, kRgTB), kRgTB, 0, s>>>(S.ccl.list_p, S.ccl.parent_p, size, nf, min_cells, sb, lab, st);
+        k_rg_size<<<cdiv(nf, kFieldTB), kFieldTB, 0, s>>>(S.ccl.parent_p, nf, size);
+        k_rg_sites<<<cdiv(nf, kFieldTB), kFieldTB, 0, s>>>(S.ccl.list_p, S.ccl.parent_p, size, nf, min_cells, sb, lab, st);
         AOS_HIP(hipGetLastError());
     }
     return nf;
@@ -315,15 +260,6 @@ int launch_components(RegionsState &S, const int8_t *d_grid, int W, int H, int m
 }  // namespace aos
 
 using namespace aos;
-
-#define AOS_RG_CATCH(tag)                                                                                            \
-    catch (const HipError &e) {                                                                                      \
-        return fail(AOS_E_HIP, std::string("HIP error ") + hipGetErrorString(e.e) + " at regions line " +            \
-                                   std::to_string(e.line) + ": " + e.what);                                          \
-    }                                                                                                                \
-    catch (const std::bad_alloc &) { return fail(AOS_E_NOMEM, "out of host memory"); }                               \
-    catch (const std::invalid_argument &e) { return fail(AOS_E_INVALID, std::string(tag ": ") + e.what()); }        \
-    catch (const std::exception &e) { return fail(AOS_E_STATE, std::string(tag ": ") + e.what()); }
 
 extern "C" int aos_gvd_regions(aos_ctx *c, const aos_path_graph *graph, const int8_t *grid, int grid_on_device,
                                const aos_grid_info *info, const int32_t *labels, const aos_regions_opts *opts,
@@ -339,47 +275,28 @@ extern "C" int aos_gvd_regions(aos_ctx *c, const aos_path_graph *graph, const in
         return fail(AOS_E_INVALID, std::string("aos_gvd_regions: ") + m);
     const int min_cells = opts ? opts->min_component_cells : 0;
     const bool want_rd = opts && opts->want_ridge_distance != 0;
-    try {
+    return guarded("regions", "aos_gvd_regions", [&]() -> int {
         DeviceScope dev_scope(c->device);
         if (!graph || !grid) c->gvd_view_settle();
-        const double *nodes_xy;
-        int32_t nn;
-        if (graph) {
-            nodes_xy = graph->nodes_xy; nn = graph->num_nodes;
-        } else {
-            if (!c->have_gvd) throw std::runtime_error("no GVD graph on this handle");
-            GvdState &gs = c->gs();
-            markers_wait(gs, false);
-            nodes_xy = gs.nodes_xy.data();
-            nn = (int32_t)gs.labels.size();
+        // the graph (only its nodes are read) and the grid; the handle's own are checked like a caller's
+        const aos_path_graph g = c->plan_graph(graph).g;
+        const double *nodes_xy = g.nodes_xy;
+        const int32_t nn = g.num_nodes;
+        if (!graph)
             if (const char *m = clr::check_graph(nodes_xy, nn, nullptr, 0)) throw std::invalid_argument(m);
-        }
         RegionsState &S = regions_state(c);
         hipStream_t s = c->stream;
-        const int8_t *d_grid = nullptr;
-        const int32_t *d_labels = nullptr;
-        aos_grid_info gi{};
-        if (grid) {
-            gi = *info;
-            const size_t C = (size_t)gi.width * gi.height;
-            if (grid_on_device) { d_grid = grid; d_labels = labels; }
-            else if (C) {
-                int8_t *d = rg_dev<int8_t>(S.d_grid, C);
-                AOS_HIP(hipMemcpyAsync(d, grid, C, hipMemcpyHostToDevice, s));
-                d_grid = d;
-                if (labels) {
-                    int32_t *dl = rg_dev<int32_t>(S.d_labels, C);
-                    AOS_HIP(hipMemcpyAsync(dl, labels, sizeof(int32_t) * C, hipMemcpyHostToDevice, s));
-                    d_labels = dl;
-                }
-            }
-        } else {
-            if (!c->have_gvd) throw std::runtime_error("no grid given and no GVD call on this handle");
-            if (c->gvd_from_frame && c->gvd_frame_gen != c->frame_gen)
-                throw std::runtime_error("the GVD graph's skeleton was replaced by a later seed-gen frame; pass the grid");
-            d_grid = c->gvd_skel;
-            gi = c->gvd_info;
+        const aos_ctx::PlanGrid pg = c->plan_grid(grid, grid_on_device, info, S.d_grid);
+        const int8_t *d_grid = pg.d_grid;
+        const aos_grid_info gi = pg.info;
+        if (!grid)
             if (const char *m = clr::check_info(gi)) throw std::invalid_argument(m);
+        const int32_t *d_labels = labels;   // (labels come with a grid, and lie where it lies: check_regions)
+        if (labels && !grid_on_device) {
+            const size_t C = (size_t)gi.width * gi.height;
+            int32_t *dl = S.d_labels.ensure_n<int32_t>(C);
+            if (C) AOS_HIP(hipMemcpyAsync(dl, labels, sizeof(int32_t) * C, hipMemcpyHostToDevice, s));
+            d_labels = dl;
         }
         S.have = false;
         S.have_rd = false;
@@ -400,16 +317,16 @@ extern "C" int aos_gvd_regions(aos_ctx *c, const aos_path_graph *graph, const in
             std::fill(h_stats, h_stats + kStWords + 1, 0u);
             h_stats[kStMaxD2] = clr::kNone;
         } else {
-            double2 *d_nodes = rg_dev<double2>(S.nodes, nn);
+            double2 *d_nodes = S.nodes.ensure_n<double2>(nn);
             if (nn) AOS_HIP(hipMemcpyAsync(d_nodes, nodes_xy, sizeof(double2) * (size_t)nn, hipMemcpyHostToDevice, s));
-            unsigned *st = rg_dev<unsigned>(S.stats, kStWords);
+            unsigned *st = S.stats.ensure_n<unsigned>(kStWords);
             AOS_HIP(hipMemsetAsync(st, 0, sizeof(unsigned) * kStWords, s));
             AOS_HIP(hipEventRecord(S.ev[0], s));
             // 1. sites and labels
             const int32_t *lab;
             const int *n_comp_dev = nullptr;
             if (d_labels) {
-                k_rg_label_sites<<<rg_cdiv(C, kRgTB), kRgTB, 0, s>>>(d_grid, d_labels, C, rg_dev<int8_t>(S.sb, C), st);
+                k_rg_label_sites<<<cdiv(C, kFieldTB), kFieldTB, 0, s>>>(d_grid, d_labels, C, S.sb.ensure_n<int8_t>(C), st);
                 lab = d_labels;
             } else {
                 nf = launch_components(S, d_grid, W, H, min_cells, st, &n_comp_dev, s);
@@ -418,26 +335,26 @@ extern "C" int aos_gvd_regions(aos_ctx *c, const aos_path_graph *graph, const in
             const int8_t *sb = S.sb.as<int8_t>();
             AOS_HIP(hipEventRecord(S.ev[1], s));
             // 2, 3. the column pass with direction, the row pass with the site
-            const int nb = rg_cdiv(H, kRgBand);
-            int16_t *off = rg_dev<int16_t>(S.off, C);
-            uint32_t *site = rg_dev<uint32_t>(S.site, C);
+            const int nb = cdiv(H, kFieldBand);
+            int16_t *off = S.off.ensure_n<int16_t>(C);
+            uint32_t *site = S.site.ensure_n<uint32_t>(C);
             clr_launch_bands(S.sf, sb, W, H, reinterpret_cast<unsigned long long *>(st + kStSites), s);
-            k_rg_cols<<<dim3(rg_cdiv(W, kRgTB), nb), kRgTB, 0, s>>>(S.sf.masks.as<unsigned long long>(), S.sf.up.as<int>(),
+            k_rg_cols<<<dim3(cdiv(W, kFieldTB), nb), kFieldTB, 0, s>>>(S.sf.masks.as<unsigned long long>(), S.sf.up.as<int>(),
                                                                    S.sf.down.as<int>(), W, H, off);
-            k_rg_rows<<<H, kRgTB, 0, s>>>(off, W, site, st + kStMaxD2);
+            k_rg_rows<<<H, kFieldTB, 0, s>>>(off, W, site, st + kStMaxD2);
             AOS_HIP(hipGetLastError());
             AOS_HIP(hipEventRecord(S.ev[2], s));
             // 4, 5. region, ridge, the ridge's distance field
-            int32_t *region = rg_dev<int32_t>(S.region, C);
-            int8_t *ridge = rg_dev<int8_t>(S.ridge, C);
-            k_rg_region<<<rg_cdiv(C, kRgTB), kRgTB, 0, s>>>(site, lab, C, region);
-            k_rg_ridge<<<rg_cdiv(C, kRgTB), kRgTB, 0, s>>>(site, region, W, H, ridge,
+            int32_t *region = S.region.ensure_n<int32_t>(C);
+            int8_t *ridge = S.ridge.ensure_n<int8_t>(C);
+            k_rg_region<<<cdiv(C, kFieldTB), kFieldTB, 0, s>>>(site, lab, C, region);
+            k_rg_ridge<<<cdiv(C, kFieldTB), kFieldTB, 0, s>>>(site, region, W, H, ridge,
                                                           reinterpret_cast<unsigned long long *>(st + kStRidge));
             AOS_HIP(hipGetLastError());
             if (want_rd) clr_launch_field(S.rf, ridge, W, H, s);
             AOS_HIP(hipEventRecord(S.ev[3], s));
             // 6. sampling and the statistics
-            k_rg_sample<<<std::max(1, rg_cdiv(nn, kRgTB)), kRgTB, 0, s>>>(
+            k_rg_sample<<<std::max(1, cdiv(nn, kFieldTB)), kFieldTB, 0, s>>>(
                 S.g, site, region, want_rd ? S.rf.d2.as<uint32_t>() : nullptr, d_nodes, nn, h_site, h_region, h_d2, h_rd2, st,
                 n_comp_dev, h_stats);
             AOS_HIP(hipGetLastError());
@@ -469,22 +386,21 @@ extern "C" int aos_gvd_regions(aos_ctx *c, const aos_path_graph *graph, const in
         out->node_ridge_offset = S.node_m.data();
         out->ms_label = ms[0]; out->ms_field = ms[1]; out->ms_ridge = ms[2]; out->ms_graph = ms[3];
         return AOS_OK;
-    }
-    AOS_RG_CATCH("aos_gvd_regions")
+    });
 }
 
 extern "C" int aos_regions_field_copy(aos_ctx *c, const char *which, void *dst, uint64_t capacity_cells) {
     if (!c) return fail(AOS_E_INVALID, "aos_regions_field_copy: null handle");
     const int f = rgn::field_of(which);
     if (f < 0) return fail(AOS_E_INVALID, "aos_regions_field_copy: which is none of site, region, ridge, ridge_d2");
-    const RegionsState *S = static_cast<const RegionsState *>(c->regions_state);
+    const RegionsState *S = c->regions_state.peek<RegionsState>();
     if (!S || !S->have) return fail(AOS_E_STATE, "aos_regions_field_copy: no aos_gvd_regions on this handle yet");
     const uint64_t C = (uint64_t)S->g.W * (uint64_t)S->g.H;
     if (f == rgn::kRidgeD2 && C && !S->have_rd)
         return fail(AOS_E_INVALID, "aos_regions_field_copy: the last aos_gvd_regions did not compute ridge_d2");
     if (capacity_cells < C) return fail(AOS_E_INVALID, "aos_regions_field_copy: capacity below width x height");
     if (C && !dst) return fail(AOS_E_INVALID, "aos_regions_field_copy: null destination");
-    try {
+    return guarded("regions", "aos_regions_field_copy", [&]() -> int {
         DeviceScope dev_scope(c->device);
         if (C) {
             const void *src[4] = {S->site.p, S->region.p, S->ridge.p, S->rf.d2.p};
@@ -492,8 +408,7 @@ extern "C" int aos_regions_field_copy(aos_ctx *c, const char *which, void *dst, 
             AOS_HIP(hipStreamSynchronize(c->stream));
         }
         return AOS_OK;
-    }
-    AOS_RG_CATCH("aos_regions_field_copy")
+    });
 }
 
 extern "C" int aos_regions_points(aos_ctx *c, const double *xy, int32_t n, uint32_t *site, int32_t *region, uint32_t *d2,
@@ -501,10 +416,10 @@ extern "C" int aos_regions_points(aos_ctx *c, const double *xy, int32_t n, uint3
     if (!c) return fail(AOS_E_INVALID, "aos_regions_points: null handle");
     if (n < 0) return fail(AOS_E_INVALID, "aos_regions_points: negative count");
     if (n > 0 && !xy) return fail(AOS_E_INVALID, "aos_regions_points: null points behind a count above 0");
-    RegionsState *S = static_cast<RegionsState *>(c->regions_state);
+    RegionsState *S = c->regions_state.peek<RegionsState>();
     if (!S || !S->have) return fail(AOS_E_STATE, "aos_regions_points: no aos_gvd_regions on this handle yet");
     if (n == 0) return AOS_OK;
-    try {
+    return guarded("regions", "aos_regions_points", [&]() -> int {
         DeviceScope dev_scope(c->device);
         const size_t N = (size_t)n;
         uint32_t *h = static_cast<uint32_t *>(S->h_pts.ensure(sizeof(uint32_t) * 4 * N));
@@ -513,9 +428,9 @@ extern "C" int aos_regions_points(aos_ctx *c, const double *xy, int32_t n, uint3
             std::fill(h + N, h + 2 * N, (uint32_t)rgn::kRegionNone);
             std::fill(h + 2 * N, h + 4 * N, clr::kNone);
         } else {
-            double2 *d_pts = rg_dev<double2>(S->pts, N);
+            double2 *d_pts = S->pts.ensure_n<double2>(N);
             AOS_HIP(hipMemcpyAsync(d_pts, xy, sizeof(double2) * N, hipMemcpyHostToDevice, c->stream));
-            k_rg_sample<<<rg_cdiv(n, kRgTB), kRgTB, 0, c->stream>>>(
+            k_rg_sample<<<cdiv(n, kFieldTB), kFieldTB, 0, c->stream>>>(
                 S->g, S->site.as<uint32_t>(), S->region.as<int32_t>(), S->have_rd ? S->rf.d2.as<uint32_t>() : nullptr, d_pts, n,
                 h, reinterpret_cast<int32_t *>(h + N), h + 2 * N, h + 3 * N, nullptr, nullptr, nullptr);
             AOS_HIP(hipGetLastError());
@@ -527,6 +442,5 @@ extern "C" int aos_regions_points(aos_ctx *c, const double *xy, int32_t n, uint3
         if (ridge_d2) std::memcpy(ridge_d2, h + 3 * N, sizeof(uint32_t) * N);
         if (ridge_offset_m) clr::to_metres(h + 3 * N, N, S->g.res, ridge_offset_m);
         return AOS_OK;
-    }
-    AOS_RG_CATCH("aos_regions_points")
+    });
 }

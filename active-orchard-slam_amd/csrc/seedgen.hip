@@ -34,14 +34,7 @@ void aos_ctx::release() {
     release_uploader();
     for (CloudSplit *sp : {&split_cur, &split_next})
         if (sp->copied) { (void)hipEventSynchronize(sp->copied); (void)hipEventDestroy(sp->copied); sp->copied = nullptr; }
-    free_path_state(path_state);   // (a void * owner: path.hip's PathState)
-    path_state = nullptr;
-    free_lin_state(lin_state);     // (linearize.hip's LinState)
-    lin_state = nullptr;
-    free_clear_state(clear_state); // (clearance.hip's ClearState)
-    clear_state = nullptr;
-    free_regions_state(regions_state); // (regions.hip's RegionsState)
-    regions_state = nullptr;
+    for (OwnedState *s : {&path_state, &lin_state, &clear_state, &regions_state}) s->reset();
     for (auto &lp : lanes) {
         markers_wait(lp->gs, false);
         lp->gs.cells.reset();

@@ -29,7 +29,6 @@
 
 namespace aos {
 
-static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 TilePlan make_tile_plan(const FrameGeom &g, float margin, int tiles_x, int tiles_y, int rank) {
     if (tiles_x < 1 || tiles_y < 1 || tiles_x > kMaxTiles || tiles_y > kMaxTiles)

@@ -2,12 +2,13 @@
 
 A scene is {"grid": int8 (H, W), "origin": (x, y), "resolution": float, "nodes": (n, 2) float64, "edges": (m, 2) int32}.
 Field scenes carry a small default graph (the corner and centre cells, joined), graph scenes a graph built for one rule
-of the sampler each. The sizes the kernels use (csrc/clearance.hip), which the sweeps run +-1 around:
-    BAND = 64        rows per band of the column pass (kClrBand)
+of the sampler each. The sizes the kernels use (csrc/field_passes.h; kClrPer: clearance.hip), which the sweeps
+run +-1 around:
+    BAND = 64        rows per band of the column pass (kFieldBand)
     WORKGROUP = 256  threads per workgroup: columns per column-pass workgroup, cells per row-pass step, nodes or edges
-                     per sampling workgroup (kClrTB)
-    BLOCK = 64       columns per block minimum of the row pass (kClrBlock)
-    ROUND = 2048     samples a sampling workgroup takes per round (kClrTB * kClrPer)
+                     per sampling workgroup (kFieldTB)
+    BLOCK = 64       columns per block minimum of the row pass (kFieldBlock)
+    ROUND = 2048     samples a sampling workgroup takes per round (kFieldTB * kClrPer)
 """
 import json
 import os

@@ -1,11 +1,11 @@
 """Designed scenes for aos_gvd_regions: the smallest shapes at which its kernels can still go wrong.
 
 A scene is clearance_scenes.scene's dict (grid, origin, resolution, nodes, edges) with two optional keys: "labels"
-(int32 (H, W): the caller-label form) and "min_component_cells". The sizes the kernels use (csrc/regions.hip), which
-the sweeps run +-1 around:
-    BAND = 64        rows per band of the column pass (kRgBand)
-    WORKGROUP = 256  threads per workgroup (kRgTB): columns per column-pass workgroup, cells per row-pass step
-    BLOCK = 64       columns per block minimum of the row pass (kRgBlock), and cells per packed occupancy word
+(int32 (H, W): the caller-label form) and "min_component_cells". The sizes the kernels use (csrc/field_passes.h;
+kCclChunk: cluster_seed.hip), which the sweeps run +-1 around:
+    BAND = 64        rows per band of the column pass (kFieldBand)
+    WORKGROUP = 256  threads per workgroup (kFieldTB): columns per column-pass workgroup, cells per row-pass step
+    BLOCK = 64       columns per block minimum of the row pass (kFieldBlock), and cells per packed occupancy word
     CHUNK = 2048     occupied cells per block-local labelling chunk (kCclChunk)
 """
 import numpy as np
