@@ -410,8 +410,10 @@ struct Planner {
         const Pt tgt = wps[target];
         const int tnode = wpn[target];
         if (tnode < 0) {   // origin return :1096-1280
+            // findNearestNode starts from DBL_MAX with a strict <: a node whose distance overflows is no
+            // node (findKNearestNodes, below, keeps such nodes)
             const std::vector<int> nn = nearest_k(tgt, 1);
-            if (nn.empty()) return;
+            if (nn.empty() || !(distance(tgt, S.nodes[nn[0]]) < std::numeric_limits<double>::max())) return;
             const std::vector<int> cands = nearest_k(start, kNearK);
             if (cands.empty()) return;
             bool found;
