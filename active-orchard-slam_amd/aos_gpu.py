@@ -156,6 +156,19 @@ REGION_NONE = -1
 REGIONS_FIELDS = {"site": np.uint32, "region": np.int32, "ridge": np.int8, "ridge_d2": np.uint32}
 
 
+class ReachOpts(ctypes.Structure):
+    _fields_ = [("min_d2", c_u), ("max_rounds", c_i)]
+
+
+class ReachOut(ctypes.Structure):
+    _fields_ = [("info", GridInfo), ("n_passable", c_u64), ("n_reached", c_u64), ("n_sources_used", c_i), ("max_cost", c_u),
+                ("cost_device", c_vp), ("num_nodes", c_i), ("node_cost", P(c_u)), ("node_metres", P(c_f)), ("n_rounds", c_i),
+                ("n_tile_runs", c_u64), ("ms_mask", c_f), ("ms_wave", c_f), ("ms_graph", c_f)]
+
+
+COST_NONE = 0xFFFFFFFF
+
+
 def path_query(initial_waypoint_reached=True, initial_waypoint=(8.0, 0.0), target=-1, saved_target=None, previous=-1,
                current=None, exploration_completed=False) -> PathQuery:
     """aos_path_gen_node state when a graph arrives (aos_path_query)."""
@@ -292,6 +305,10 @@ def lib():
         L.aos_gvd_regions.argtypes = [c_vp, P(PathGraph), c_vp, c_i, P(GridInfo), c_vp, P(RegionsOpts), P(RegionsOut)]
         L.aos_regions_field_copy.argtypes = [c_vp, ctypes.c_char_p, c_vp, c_u64]
         L.aos_regions_points.argtypes = [c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp]
+        L.aos_gvd_reach.argtypes = [c_vp, P(PathGraph), c_vp, c_i, P(GridInfo), c_vp, c_i, P(ReachOpts), P(ReachOut)]
+        L.aos_reach_field_copy.argtypes = [c_vp, c_vp, c_u64]
+        L.aos_reach_points.argtypes = [c_vp, c_vp, c_i, c_vp, c_vp]
+        L.aos_reach_descend.argtypes = [c_vp, c_vp, c_vp, c_vp, c_u64, P(c_u64)]
         L.aos_group_create.argtypes = [P(Params), P(c_i), c_i, c_i, P(c_vp)]
         L.aos_group_destroy.argtypes = [c_vp]
         L.aos_group_set_polygon.argtypes = [c_vp, c_vp, c_u]
@@ -678,6 +695,72 @@ class Ctx:
         _check(lib().aos_regions_points(self.h, a.ctypes.data if n else None, n,
                                         *[v.ctypes.data if n else None for v in r.values()]))
         return r
+
+    def gvd_reach(self, sources, graph: dict | None = None, grid=None, info: dict | None = None, on_device: bool = False,
+                  min_d2: int = 0, max_rounds: int = 0) -> dict:
+        """The clearance-limited cost-to-go field of `grid` from the world points `sources` (n, 2): 5 per axis move, 7
+        per diagonal move, through the cells that are not occupied and whose clearance d2 is at least min_d2, and the
+        costs at the graph's nodes (aos_gvd_reach). graph, grid, info and on_device as in gvd_clearance. max_rounds > 0:
+        the call fails if the field has not settled after that many rounds."""
+        gs, keep = None, []
+        if graph is not None:
+            nodes = np.ascontiguousarray(graph["nodes"], dtype=np.float64).reshape(-1)
+            gs = PathGraph()
+            gs.num_nodes, gs.nodes_xy = nodes.size // 2, nodes.ctypes.data_as(P(c_d))
+            keep.append(nodes)
+        gi, gp = None, None
+        if grid is not None:
+            gi = GridInfo(info["origin"][0], info["origin"][1], info["resolution"], info["width"], info["height"])
+            if on_device:
+                gp = c_vp(int(grid))
+            else:
+                keep.append(np.ascontiguousarray(grid, dtype=np.int8).reshape(-1))
+                gp = c_vp(keep[-1].ctypes.data or 1)   # (an empty grid is still a grid, not the NULL form)
+        src = np.ascontiguousarray(sources, dtype=np.float64).reshape(-1, 2)
+        opts = ReachOpts(int(min_d2), int(max_rounds))
+        o = ReachOut()
+        _check(lib().aos_gvd_reach(self.h, ctypes.byref(gs) if gs is not None else None, gp, int(on_device),
+                                   ctypes.byref(gi) if gi is not None else None, src.ctypes.data if len(src) else None,
+                                   len(src), ctypes.byref(opts), ctypes.byref(o)))
+        del keep
+        self._reach_shape = (o.info.height, o.info.width)
+        nn = o.num_nodes
+        return {"origin": (o.info.origin_x, o.info.origin_y), "resolution": o.info.resolution, "width": o.info.width,
+                "height": o.info.height, "n_passable": o.n_passable, "n_reached": o.n_reached,
+                "n_sources_used": o.n_sources_used, "max_cost": o.max_cost, "cost_device": o.cost_device,
+                "node_cost": _arr(o.node_cost, nn, np.uint32), "node_metres": _arr(o.node_metres, nn, np.float32),
+                "n_rounds": o.n_rounds, "n_tile_runs": o.n_tile_runs,
+                "ms": {"mask": o.ms_mask, "wave": o.ms_wave, "graph": o.ms_graph}}
+
+    def reach_field(self) -> np.ndarray:
+        """The last gvd_reach's field as a (height, width) uint32 array (aos_reach_field_copy)."""
+        out = np.empty(getattr(self, "_reach_shape", (0, 0)), np.uint32)
+        _check(lib().aos_reach_field_copy(self.h, out.ctypes.data or None, out.size))
+        return out
+
+    def reach_points(self, xy) -> tuple:
+        """(cost, metres) of points (n, 2) against the last gvd_reach's field (aos_reach_points)."""
+        a = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        n = len(a)
+        cost, m = np.empty(n, np.uint32), np.empty(n, np.float32)
+        _check(lib().aos_reach_points(self.h, a.ctypes.data if n else None, n, cost.ctypes.data if n else None,
+                                      m.ctypes.data if n else None))
+        return cost, m
+
+    def reach_descend(self, start, capacity: int | None = None) -> dict:
+        """The descent from the world point `start` on the last gvd_reach's field (aos_reach_descend): "cells" (linear
+        indices), "xy" (their centres) and "n_cells", the full length. capacity None: room for the whole descent (asked
+        for first); else at most that many cells are returned."""
+        s = np.ascontiguousarray(start, dtype=np.float64).reshape(2)
+        n = c_u64(0)
+        if capacity is None:
+            _check(lib().aos_reach_descend(self.h, s.ctypes.data, None, None, 0, ctypes.byref(n)))
+            capacity = n.value
+        cells, xy = np.empty(capacity, np.uint32), np.empty((capacity, 2), np.float64)
+        _check(lib().aos_reach_descend(self.h, s.ctypes.data, cells.ctypes.data if capacity else None,
+                                       xy.ctypes.data if capacity else None, capacity, ctypes.byref(n)))
+        k = min(capacity, n.value)
+        return {"cells": cells[:k], "xy": xy[:k], "n_cells": n.value}
 
     def cloud_prefetch(self, cloud, n_points: int | None = None, point_step=16, offs=(0, 4, 8), is_dense=True) -> None:
         """Start uploading a host PointCloud2 for the next seedgen() of the same array (aos_cloud_prefetch)."""

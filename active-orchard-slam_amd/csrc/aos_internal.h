@@ -111,7 +111,7 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
-// A state that one file defines and the handle owns (PathState, LinState, ClearState, RegionsState): get<T>()
+// A state that one file defines and the handle owns (PathState, LinState, ClearState, RegionsState, ReachState): get<T>()
 // creates it on first use and sets the deleter with it, so aos_ctx needs no declaration of T.
 struct OwnedState {
     void *p = nullptr;
@@ -260,8 +260,8 @@ struct TilePlan {
 };
 // the poses (x, y, qz, qw) of the last aos_path_plan on the state (none after "Failed"); false: no plan has run
 bool path_last_poses(const OwnedState &path_state, const double **poses, int *n);   // path.hip
-// The distance field's buffers and launches (clearance.hip), shared with regions.hip, which runs them on its own
-// buffers: masks / up / down = the (64-row band, column) occupancy words and the nearest occupied row above / below
+// The distance field's buffers and launches (clearance.hip), shared with regions.hip and reach.hip, which run them on
+// their own buffers: masks / up / down = the (64-row band, column) occupancy words and the nearest occupied row above / below
 // each band; g = the column distances; d2 = the field; stats = the occupied count (8 bytes) and the maximum.
 struct ClrFieldBufs { DevBuf masks, up, down, g, d2, stats; };
 void clr_launch_bands(ClrFieldBufs &B, const int8_t *d_grid, int W, int H, unsigned long long *n_occ, hipStream_t s);

@@ -575,6 +575,80 @@ int aos_regions_field_copy(aos_ctx *ctx, const char *which, void *dst, uint64_t 
 int aos_regions_points(aos_ctx *ctx, const double *xy, int32_t n, uint32_t *site, int32_t *region, uint32_t *d2,
                        uint32_t *ridge_d2, float *ridge_offset_m);
 
+/* ---------------------------------------------------------------------------------------------
+ * Clearance-limited cost-to-go. aos_gvd_clearance and aos_gvd_regions are straight-line quantities; aos_gvd_reach is
+ * the field that knows obstacles are in the way: for a robot that must keep a given distance from every occupied
+ * cell, which cells and graph nodes it can reach from a set of sources, how far it is to drive there, and along which
+ * cells. Every quantity is an integer: the definitions below fix every word of the result.
+ *  - Grid: int8 bytes with `info`, width, height <= 16384; a cell is occupied iff its byte is 100. The linear index of
+ *    cell (x, y) is y * width + x.
+ *  - Passable: a cell is passable iff its byte is not 100 and its d2 >= opts.min_d2, d2 being aos_gvd_clearance's
+ *    field of the same grid (AOS_D2_NONE counts as >= anything). With min_d2 <= 1 the second condition follows from
+ *    the first, and no distance field is computed. n_passable = the passable cells.
+ *  - Moves: from a passable cell to a passable 8-neighbour inside the grid. An axis move costs 5, a diagonal move 7;
+ *    a diagonal move from (x, y) to (x + dx, y + dy) is allowed only if (x + dx, y) and (x, y + dy) are passable too
+ *    (no corner cutting). The move relation is symmetric.
+ *  - Sources: n_sources world points (x, y), 0 <= n_sources <= 2^20, each mapped to its cell by the cell rule of
+ *    aos_gvd_clearance. A source that is not finite, has no cell or falls on an impassable cell is dropped.
+ *    n_sources_used = the sources kept (sources, not distinct cells: duplicates count).
+ *  - Cost: cost[c] = the least sum of move costs from any source cell to c, uint32; 0 at a source cell; AOS_COST_NONE
+ *    at an impassable cell and at a passable cell that no source reaches. width * height <= 2^28, so every finite
+ *    cost is below 7 * 2^28 < 2^31. n_reached = the cells with a finite cost; max_cost = the largest finite cost,
+ *    AOS_COST_NONE if n_reached == 0.
+ *  - Nodes and points: the cost at the node's or point's cell, AOS_COST_NONE without a cell. Metres:
+ *    (float)((double)cost * res / 5.0), +inf for AOS_COST_NONE.
+ *  - Descent from a start point whose cell c has a finite cost: the cell sequence starts at c; each further cell is
+ *    the first neighbour n reachable by an allowed move with cost[n] + w(c, n) == cost[c], the neighbours (dx, dy)
+ *    tried in the order (1,0), (-1,0), (0,1), (0,-1), (1,1), (-1,1), (1,-1), (-1,-1); one always exists. The sequence
+ *    ends at the first cell of cost 0 and has at most cost / 5 + 1 cells. A start without a cell or with cost
+ *    AOS_COST_NONE has 0 cells.
+ * graph and grid = NULL are those of aos_gvd_clearance (the handle's last GVD graph, of which only nodes_xy and
+ * num_nodes are read; the skeleton that graph was built on), with AOS_E_STATE under the same conditions. opts = NULL
+ * is {0, 0}. AOS_E_INVALID: every grid and info case of aos_gvd_clearance, n_sources negative or above 2^20, a null
+ * sources_xy behind a positive count. width * height = 0: status 0, nothing launched, the counts 0, max_cost
+ * AOS_COST_NONE, cost_device NULL, every node value AOS_COST_NONE / +inf.
+ * The field is computed as a fixed point in rounds (n_rounds: the rounds in which some tile of the grid ran); the
+ * call returns once a round ran no tile. opts.max_rounds > 0: at most that many rounds are issued, and if a tile still
+ * ran in the last of them the call fails with AOS_E_STATE, "reach did not converge in N rounds", and leaves no field
+ * behind (aos_reach_field_copy: AOS_E_STATE). Every call recomputes its field; the outputs are library-owned and valid
+ * until the next aos_gvd_reach on the handle or aos_destroy. The call has buffers of its own: the fields of earlier
+ * aos_gvd_clearance and aos_gvd_regions calls stay valid across it.
+ * ------------------------------------------------------------------------------------------- */
+#define AOS_COST_NONE 0xFFFFFFFFu
+typedef struct aos_reach_opts {
+    uint32_t min_d2;        /* a passable cell's d2 is at least this (<= 1: every free cell is passable)          */
+    int32_t max_rounds;     /* <= 0: no limit                                                                      */
+} aos_reach_opts;
+typedef struct aos_reach_out {
+    aos_grid_info info;
+    uint64_t n_passable, n_reached;
+    int32_t n_sources_used;
+    uint32_t max_cost;                               /* AOS_COST_NONE if n_reached == 0                        */
+    const uint32_t *cost_device;                     /* width * height words on the handle's GPU               */
+    int32_t num_nodes;
+    const uint32_t *node_cost;                       /* host, library-owned                                    */
+    const float *node_metres;
+    int32_t n_rounds;                                /* diagnostics, not part of the definition                */
+    uint64_t n_tile_runs;                            /* tile workgroups that ran, over all rounds              */
+    float ms_mask, ms_wave, ms_graph;                /* device time: mask and seeding (with the distance field
+                                                        where min_d2 >= 2) / the rounds / statistics, sampling */
+} aos_reach_out;
+int aos_gvd_reach(aos_ctx *ctx, const aos_path_graph *graph, const int8_t *grid, int grid_on_device,
+                  const aos_grid_info *info, const double *sources_xy, int32_t n_sources, const aos_reach_opts *opts,
+                  aos_reach_out *out);
+/* The last aos_gvd_reach's field copied to host memory. AOS_E_STATE before any field exists; AOS_E_INVALID for a
+ * capacity_cells below width * height or a null dst behind cells. */
+int aos_reach_field_copy(aos_ctx *ctx, uint32_t *dst, uint64_t capacity_cells);
+/* cost and metres of n points (x, y) against the last aos_gvd_reach's field, by the node rule. Either output may be
+ * null. AOS_E_STATE before any field exists; a non-finite point has no cell. */
+int aos_reach_points(aos_ctx *ctx, const double *xy, int32_t n, uint32_t *cost, float *metres);
+/* The descent from start_xy on the last aos_gvd_reach's field: the cells' linear indices into cells and, if xy is not
+ * null, their centres origin + (index + 0.5) * res as doubles (x, y) into xy; at most capacity_cells of them are
+ * written, and *n_cells is always the full length. AOS_E_STATE before any field exists; AOS_E_INVALID for a null
+ * start_xy or n_cells, or a null cells behind a capacity above 0. */
+int aos_reach_descend(aos_ctx *ctx, const double start_xy[2], uint32_t *cells, double *xy, uint64_t capacity_cells,
+                      uint64_t *n_cells);
+
 /* Diagnostics: copy an internal device grid of the last frame to host as int8 {0,100}.
  * which: "raster", "inflated", "opened", "skeleton_frameless". */
 int aos_debug_grid(aos_ctx *ctx, const char *which, int8_t *dst, uint64_t capacity);
