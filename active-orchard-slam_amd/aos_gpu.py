@@ -169,6 +169,16 @@ class ReachOut(ctypes.Structure):
 COST_NONE = 0xFFFFFFFF
 
 
+class PullOpts(ctypes.Structure):
+    _fields_ = [("max_span", c_i)]
+
+
+class PullOut(ctypes.Structure):
+    _fields_ = [("n_cells", c_u64), ("start_cost", c_u), ("n_waypoints", c_i), ("waypoint_steps", P(c_u)),
+                ("waypoint_cells", P(c_u)), ("waypoints_xy", P(c_d)), ("length_m", c_d), ("descent_m", c_d),
+                ("n_steps_launched", c_i), ("n_sight_tests", c_u64), ("ms_descend", c_f), ("ms_pull", c_f)]
+
+
 def path_query(initial_waypoint_reached=True, initial_waypoint=(8.0, 0.0), target=-1, saved_target=None, previous=-1,
                current=None, exploration_completed=False) -> PathQuery:
     """aos_path_gen_node state when a graph arrives (aos_path_query)."""
@@ -309,6 +319,8 @@ def lib():
         L.aos_reach_field_copy.argtypes = [c_vp, c_vp, c_u64]
         L.aos_reach_points.argtypes = [c_vp, c_vp, c_i, c_vp, c_vp]
         L.aos_reach_descend.argtypes = [c_vp, c_vp, c_vp, c_vp, c_u64, P(c_u64)]
+        L.aos_reach_sight.argtypes = [c_vp, c_vp, c_vp, c_i, c_vp, c_vp]
+        L.aos_reach_pull.argtypes = [c_vp, c_vp, P(PullOpts), P(PullOut)]
         L.aos_group_create.argtypes = [P(Params), P(c_i), c_i, c_i, P(c_vp)]
         L.aos_group_destroy.argtypes = [c_vp]
         L.aos_group_set_polygon.argtypes = [c_vp, c_vp, c_u]
@@ -761,6 +773,32 @@ class Ctx:
                                        xy.ctypes.data if capacity else None, capacity, ctypes.byref(n)))
         k = min(capacity, n.value)
         return {"cells": cells[:k], "xy": xy[:k], "n_cells": n.value}
+
+    def reach_sight(self, from_xy, to_xy) -> tuple:
+        """(n_touched, n_blocked) of the straight segments from_xy[k] -> to_xy[k] (n, 2) against the last gvd_reach's
+        passable mask (aos_reach_sight): a segment is free iff n_blocked is 0; an end without a cell gives
+        (0, COST_NONE)."""
+        a = np.ascontiguousarray(from_xy, dtype=np.float64).reshape(-1, 2)
+        b = np.ascontiguousarray(to_xy, dtype=np.float64).reshape(-1, 2)
+        if len(a) != len(b):
+            raise ValueError("from_xy and to_xy differ in length")
+        n = len(a)
+        touched, blocked = np.empty(n, np.uint32), np.empty(n, np.uint32)
+        _check(lib().aos_reach_sight(self.h, a.ctypes.data if n else None, b.ctypes.data if n else None, n,
+                                     touched.ctypes.data if n else None, blocked.ctypes.data if n else None))
+        return touched, blocked
+
+    def reach_pull(self, start, max_span: int = 0) -> dict:
+        """The descent from the world point `start` pulled taut (aos_reach_pull): "steps", "cells" and "xy" of the
+        farthest-visible waypoints, "n_cells", "start_cost", "length_m", "descent_m" and the diagnostics."""
+        s = np.ascontiguousarray(start, dtype=np.float64).reshape(2)
+        opts, o = PullOpts(int(max_span)), PullOut()
+        _check(lib().aos_reach_pull(self.h, s.ctypes.data, ctypes.byref(opts), ctypes.byref(o)))
+        n = o.n_waypoints
+        return {"n_cells": o.n_cells, "start_cost": o.start_cost, "steps": _arr(o.waypoint_steps, n, np.uint32),
+                "cells": _arr(o.waypoint_cells, n, np.uint32), "xy": _arr(o.waypoints_xy, 2 * n, np.float64).reshape(-1, 2),
+                "length_m": o.length_m, "descent_m": o.descent_m, "n_steps_launched": o.n_steps_launched,
+                "n_sight_tests": o.n_sight_tests, "ms": {"descend": o.ms_descend, "pull": o.ms_pull}}
 
     def cloud_prefetch(self, cloud, n_points: int | None = None, point_step=16, offs=(0, 4, 8), is_dense=True) -> None:
         """Start uploading a host PointCloud2 for the next seedgen() of the same array (aos_cloud_prefetch)."""

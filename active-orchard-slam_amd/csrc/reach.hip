@@ -30,6 +30,7 @@
 #include "aos_ctx.h"
 #include "field_passes.h"
 #include "reach.h"
+#include "reach_state.h"
 
 namespace aos {
 
@@ -252,19 +253,11 @@ __global__ void __launch_bounds__(64) k_rc_descend(const uint32_t *cost, int W, 
     if (lane == 0) *n_out = len;
 }
 
-struct ReachState {
-    ClrFieldBufs f;   // the distance field behind the mask (min_d2 >= 2), this state's own
-    DevBuf d_grid, pass, cost, flags, ran, stats, nodes, src, pts, path;
-    PinnedBuf h_peek, h_out, h_pts, h_path;
-    std::vector<float> node_m;
-    hipEvent_t ev[4] = {};
-    bool have = false;
-    clr::Grid g{};
-    aos_grid_info info{};
-    ~ReachState() {
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
-};
+void rc_launch_descend(const ReachState &S, int x, int y, uint32_t *cells, unsigned long long cap,
+                       unsigned long long max_len, unsigned long long *n_out, hipStream_t s) {
+    k_rc_descend<<<1, 64, 0, s>>>(S.cost.as<uint32_t>(), S.g.W, S.g.H, x, y, cells, cap, max_len, n_out);
+    AOS_HIP(hipGetLastError());
+}
 
 namespace {
 
@@ -444,7 +437,7 @@ extern "C" int aos_reach_descend(aos_ctx *c, const double start_xy[2], uint32_t 
     return guarded("reach", "aos_reach_descend", [&]() -> int {
         DeviceScope dev_scope(c->device);
         hipStream_t s = c->stream;
-        const int W = S->g.W, H = S->g.H;
+        const int W = S->g.W;
         // the start's cost bounds the length, and so the device buffer
         unsigned long long *h = static_cast<unsigned long long *>(S->h_path.ensure(sizeof(unsigned long long) * 2));
         uint32_t start_cost = rch::kNone;
@@ -454,8 +447,7 @@ extern "C" int aos_reach_descend(aos_ctx *c, const double start_xy[2], uint32_t 
         const unsigned long long max_len = (unsigned long long)start_cost / rch::kAxis + 1;
         const unsigned long long cap = std::min<unsigned long long>(capacity_cells, max_len);
         uint32_t *d_cells = S->path.ensure_n<uint32_t>(cap);
-        k_rc_descend<<<1, 64, 0, s>>>(S->cost.as<uint32_t>(), W, H, mx, my, d_cells, cap, max_len, h);
-        AOS_HIP(hipGetLastError());
+        rc_launch_descend(*S, mx, my, d_cells, cap, max_len, h, s);
         AOS_HIP(hipStreamSynchronize(s));
         const unsigned long long len = h[0], wrote = std::min(len, cap);
         if (wrote) AOS_HIP(hipMemcpy(cells, d_cells, sizeof(uint32_t) * wrote, hipMemcpyDeviceToHost));

@@ -649,6 +649,65 @@ int aos_reach_points(aos_ctx *ctx, const double *xy, int32_t n, uint32_t *cost, 
 int aos_reach_descend(aos_ctx *ctx, const double start_xy[2], uint32_t *cells, double *xy, uint64_t capacity_cells,
                       uint64_t *n_cells);
 
+/* ---------------------------------------------------------------------------------------------
+ * Line of sight and taut descents. A descent is a staircase of 8-connected cells; aos_reach_sight answers whether a
+ * robot that keeps reach's clearance can drive a straight segment, and aos_reach_pull turns a descent into the few
+ * waypoints a controller wants while every leg keeps that clearance. Everything is integer, as above: the definitions
+ * fix every word of the result.
+ *  - Passable is the mask of the last successful aos_gvd_reach on the handle (its grid, its min_d2). Both calls return
+ *    AOS_E_STATE before any aos_gvd_reach on the handle and after one that failed ("did not converge").
+ *  - Touched cells: for cells a = (ax, ay) and b = (bx, by) let dx = bx - ax, dy = by - ay. T(a, b) is the set of
+ *    cells (x, y) with min(ax, bx) <= x <= max(ax, bx), min(ay, by) <= y <= max(ay, by) and
+ *        2 * |dx * (y - ay) - dy * (x - ax)| <= |dx| + |dy|.
+ *    Every term is below 2^30 (width, height <= 16384). These are exactly the cells whose closed unit square meets
+ *    the closed segment between the two centres. T contains a and b; T(a, a) = {a}; T(a, b) = T(b, a); an axis
+ *    segment of n steps touches n + 1 cells, a pure diagonal of n steps 3 n + 1 (the two cells beside every corner it
+ *    passes through included); (0,0)->(2,1) touches 4 cells, (0,0)->(6,3) touches 10. A move of aos_gvd_reach is
+ *    allowed iff the segment between the two cells touches only passable cells: the corner rule is the diagonal case.
+ *  - aos_reach_sight: n segments, from_xy and to_xy n points (x, y) each, every end mapped to its cell by the cell
+ *    rule of aos_gvd_clearance. n_touched[k] = |T|; n_blocked[k] = the cells of T that are not passable: the segment is
+ *    free iff it is 0. An end that is not finite or has no cell gives n_touched 0 and n_blocked AOS_COST_NONE. Either
+ *    output may be null. n = 0: AOS_OK, nothing launched. AOS_E_INVALID: n negative, a null array behind a positive n.
+ *  - aos_reach_pull: let c_0 .. c_(m-1) be the descent of aos_reach_descend from start_xy (m = 0 when the start has no
+ *    cell or no finite cost). The waypoints are the steps k_0 = 0 and, while k_i < m - 1,
+ *        k_(i+1) = max { j : k_i < j <= hi and n_blocked(c_(k_i), c_j) = 0 },
+ *    hi = m - 1 when opts.max_span <= 0, else min(m - 1, k_i + max_span). The set is never empty, since j = k_i + 1 is
+ *    an allowed move. The rule is the farthest visible step, not the step before the first invisible one: visibility
+ *    along a descent is not monotone. opts = NULL is {0}.
+ *    n_cells = m; start_cost = the start cell's cost (AOS_COST_NONE for m = 0); n_waypoints (0 for m = 0, 1 for
+ *    m = 1); waypoint_steps = the k_i; waypoint_cells = the linear indices of c_(k_i); waypoints_xy = their centres
+ *    origin + (index + 0.5) * res; length_m = the sum over the legs in order of sqrt((double)(dx^2 + dy^2)),
+ *    accumulated in double, times res once at the end (0 for fewer than two waypoints); descent_m =
+ *    (double)start_cost * res / 5 (+inf for m = 0). Both are host arithmetic on the integers.
+ *    m > 65536 is AOS_E_INVALID, "descent longer than 65536 cells" (aos_path_linearize's limit on its poses), and
+ *    leaves nothing behind. The pull's worst case is quadratic in m; this limit and max_span are the caller's bound.
+ *    AOS_E_INVALID also for a null start_xy or out.
+ *    The outputs are library-owned, in buffers of their own, and valid until the next aos_reach_pull or aos_gvd_reach on
+ *    the handle or aos_destroy; the field and the outputs of the other reach calls are not touched.
+ * Guarantee: every cell touched by every leg is passable. So the robot's centre keeps reach's clearance along the
+ * whole polyline, quantised to the grid as aos_gvd_clearance is. Neither the staircase of cell centres joined by
+ * anything but its own moves nor a regressed segment of aos_path_linearize gives this.
+ * ------------------------------------------------------------------------------------------- */
+int aos_reach_sight(aos_ctx *ctx, const double *from_xy, const double *to_xy, int32_t n, uint32_t *n_touched,
+                    uint32_t *n_blocked);
+typedef struct aos_pull_opts {
+    int32_t max_span;       /* > 0: a leg spans at most this many steps of the descent; <= 0: no limit           */
+} aos_pull_opts;
+typedef struct aos_pull_out {
+    uint64_t n_cells;                                /* m, the descent's length                                 */
+    uint32_t start_cost;                             /* AOS_COST_NONE for m = 0                                 */
+    int32_t n_waypoints;
+    const uint32_t *waypoint_steps;                  /* host, library-owned: n_waypoints words each             */
+    const uint32_t *waypoint_cells;
+    const double *waypoints_xy;                      /* n_waypoints x (x, y)                                    */
+    double length_m, descent_m;
+    int32_t n_steps_launched;                        /* diagnostics, not part of the definition: anchor steps   */
+    uint64_t n_sight_tests;                          /* candidates the anchor steps tested                      */
+    float ms_descend, ms_pull;                       /* stream time: the descent / the anchor steps with their
+                                                        host looks                                              */
+} aos_pull_out;
+int aos_reach_pull(aos_ctx *ctx, const double start_xy[2], const aos_pull_opts *opts, aos_pull_out *out);
+
 /* Diagnostics: copy an internal device grid of the last frame to host as int8 {0,100}.
  * which: "raster", "inflated", "opened", "skeleton_frameless". */
 int aos_debug_grid(aos_ctx *ctx, const char *which, int8_t *dst, uint64_t capacity);
