@@ -179,6 +179,20 @@ class PullOut(ctypes.Structure):
                 ("n_steps_launched", c_i), ("n_sight_tests", c_u64), ("ms_descend", c_f), ("ms_pull", c_f)]
 
 
+class WidthOpts(ctypes.Structure):
+    _fields_ = [("max_rounds", c_i)]
+
+
+class WidthOut(ctypes.Structure):
+    _fields_ = [("info", GridInfo), ("n_free", c_u64), ("n_reached", c_u64), ("n_sources_used", c_i), ("min_width", c_u),
+                ("max_width", c_u), ("width_device", c_vp), ("num_nodes", c_i), ("node_width", P(c_u)),
+                ("node_radius_m", P(c_f)), ("n_rounds", c_i), ("n_tile_runs", c_u64), ("ms_field", c_f), ("ms_wave", c_f),
+                ("ms_graph", c_f)]
+
+
+WIDTH_NONE = 0
+
+
 def path_query(initial_waypoint_reached=True, initial_waypoint=(8.0, 0.0), target=-1, saved_target=None, previous=-1,
                current=None, exploration_completed=False) -> PathQuery:
     """aos_path_gen_node state when a graph arrives (aos_path_query)."""
@@ -321,6 +335,9 @@ def lib():
         L.aos_reach_descend.argtypes = [c_vp, c_vp, c_vp, c_vp, c_u64, P(c_u64)]
         L.aos_reach_sight.argtypes = [c_vp, c_vp, c_vp, c_i, c_vp, c_vp]
         L.aos_reach_pull.argtypes = [c_vp, c_vp, P(PullOpts), P(PullOut)]
+        L.aos_gvd_width.argtypes = [c_vp, P(PathGraph), c_vp, c_i, P(GridInfo), c_vp, c_i, P(WidthOpts), P(WidthOut)]
+        L.aos_width_field_copy.argtypes = [c_vp, c_vp, c_u64]
+        L.aos_width_points.argtypes = [c_vp, c_vp, c_i, c_vp, c_vp]
         L.aos_group_create.argtypes = [P(Params), P(c_i), c_i, c_i, P(c_vp)]
         L.aos_group_destroy.argtypes = [c_vp]
         L.aos_group_set_polygon.argtypes = [c_vp, c_vp, c_u]
@@ -799,6 +816,57 @@ class Ctx:
                 "cells": _arr(o.waypoint_cells, n, np.uint32), "xy": _arr(o.waypoints_xy, 2 * n, np.float64).reshape(-1, 2),
                 "length_m": o.length_m, "descent_m": o.descent_m, "n_steps_launched": o.n_steps_launched,
                 "n_sight_tests": o.n_sight_tests, "ms": {"descend": o.ms_descend, "pull": o.ms_pull}}
+
+    def gvd_width(self, sources, graph: dict | None = None, grid=None, info: dict | None = None, on_device: bool = False,
+                  max_rounds: int = 0) -> dict:
+        """For every cell of `grid` the widest robot that can get there from the world points `sources` (n, 2), as the
+        squared clearance (in cells) it keeps on its best way, and the values at the graph's nodes (aos_gvd_width):
+        width >= m exactly where gvd_reach(min_d2=m) from the same sources arrives. graph, grid, info and on_device as in
+        gvd_clearance. max_rounds > 0: the call fails if the field has not settled after that many rounds."""
+        gs, keep = None, []
+        if graph is not None:
+            nodes = np.ascontiguousarray(graph["nodes"], dtype=np.float64).reshape(-1)
+            gs = PathGraph()
+            gs.num_nodes, gs.nodes_xy = nodes.size // 2, nodes.ctypes.data_as(P(c_d))
+            keep.append(nodes)
+        gi, gp = None, None
+        if grid is not None:
+            gi = GridInfo(info["origin"][0], info["origin"][1], info["resolution"], info["width"], info["height"])
+            if on_device:
+                gp = c_vp(int(grid))
+            else:
+                keep.append(np.ascontiguousarray(grid, dtype=np.int8).reshape(-1))
+                gp = c_vp(keep[-1].ctypes.data or 1)   # (an empty grid is still a grid, not the NULL form)
+        src = np.ascontiguousarray(sources, dtype=np.float64).reshape(-1, 2)
+        opts = WidthOpts(int(max_rounds))
+        o = WidthOut()
+        _check(lib().aos_gvd_width(self.h, ctypes.byref(gs) if gs is not None else None, gp, int(on_device),
+                                   ctypes.byref(gi) if gi is not None else None, src.ctypes.data if len(src) else None,
+                                   len(src), ctypes.byref(opts), ctypes.byref(o)))
+        del keep
+        self._width_shape = (o.info.height, o.info.width)
+        nn = o.num_nodes
+        return {"origin": (o.info.origin_x, o.info.origin_y), "resolution": o.info.resolution, "width": o.info.width,
+                "height": o.info.height, "n_free": o.n_free, "n_reached": o.n_reached,
+                "n_sources_used": o.n_sources_used, "min_width": o.min_width, "max_width": o.max_width,
+                "width_device": o.width_device, "node_width": _arr(o.node_width, nn, np.uint32),
+                "node_radius_m": _arr(o.node_radius_m, nn, np.float32), "n_rounds": o.n_rounds,
+                "n_tile_runs": o.n_tile_runs, "ms": {"field": o.ms_field, "wave": o.ms_wave, "graph": o.ms_graph}}
+
+    def width_field(self) -> np.ndarray:
+        """The last gvd_width's field as a (height, width) uint32 array (aos_width_field_copy)."""
+        out = np.empty(getattr(self, "_width_shape", (0, 0)), np.uint32)
+        _check(lib().aos_width_field_copy(self.h, out.ctypes.data or None, out.size))
+        return out
+
+    def width_points(self, xy) -> tuple:
+        """(width, radius_m) of points (n, 2) against the last gvd_width's field (aos_width_points)."""
+        a = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        n = len(a)
+        w, r = np.empty(n, np.uint32), np.empty(n, np.float32)
+        _check(lib().aos_width_points(self.h, a.ctypes.data if n else None, n, w.ctypes.data if n else None,
+                                      r.ctypes.data if n else None))
+        return w, r
 
     def cloud_prefetch(self, cloud, n_points: int | None = None, point_step=16, offs=(0, 4, 8), is_dense=True) -> None:
         """Start uploading a host PointCloud2 for the next seedgen() of the same array (aos_cloud_prefetch)."""

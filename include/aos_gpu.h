@@ -708,6 +708,72 @@ typedef struct aos_pull_out {
 } aos_pull_out;
 int aos_reach_pull(aos_ctx *ctx, const double start_xy[2], const aos_pull_opts *opts, aos_pull_out *out);
 
+/* ---------------------------------------------------------------------------------------------
+ * The widest robot that can reach each cell and node. aos_gvd_reach answers "given this robot, where can it go?" for
+ * one clearance threshold; aos_gvd_width answers the inverse for every cell and node at once: the largest min_d2 at
+ * which aos_gvd_reach from the same sources still reaches it. It is the max-min (bottleneck) closure of
+ * aos_gvd_clearance's d2 over aos_gvd_reach's move relation. Every quantity is an integer: the definitions below fix
+ * every word of the result and no algorithm does.
+ *  - Grid, cell rule, info and graph checks: aos_gvd_clearance's.
+ *  - cap[c]: 0 if the cell's byte is 100; otherwise aos_gvd_clearance's d2[c] of the same grid, which is at least 1,
+ *    and AOS_D2_NONE = 0xFFFFFFFF everywhere when no cell is occupied, which is simply the largest value.
+ *  - Moves: aos_gvd_reach's, to an 8-neighbour inside the grid. The bottleneck of an axis move a -> b is
+ *    min(cap[a], cap[b]); of a diagonal move min(cap[a], cap[b], cap[(bx, ay)], cap[(ax, by)]): the two cells beside
+ *    the diagonal count (aos_gvd_reach's corner rule). The relation is symmetric.
+ *  - Sources: as aos_gvd_reach, 0 <= n_sources <= 2^20 world points mapped by the cell rule. A source that is not
+ *    finite, has no cell or has cap 0 is dropped. n_sources_used = the sources kept (duplicates count).
+ *  - width[c], uint32: the maximum, over all move paths from a kept source cell to c, of the minimum bottleneck along
+ *    the path; a path of one cell has value cap[c]. 0 (AOS_WIDTH_NONE) if no path has a bottleneck above 0: occupied
+ *    cells, and free cells that no source can reach, have width 0.
+ *  - Equivalence: for every m >= 1, width[c] >= m iff aos_gvd_reach on the same grid and sources with min_d2 = m gives
+ *    c a finite cost (for m <= 1 reach's passable is "byte != 100", which is width >= 1).
+ *  - Counts: n_free = the cells with cap > 0; n_reached = the cells with width > 0; max_width and min_width run over
+ *    the reached cells and are 0 when there are none.
+ *  - Nodes and points: the width at the node's or point's cell by the node rule, 0 without a cell. radius_m =
+ *    (float)(sqrt((double)width) * res), +inf for 0xFFFFFFFF and 0.0f for 0: host arithmetic on the integer, the form of
+ *    aos_gvd_clearance's metres.
+ * graph and grid = NULL are the handle's own, as in aos_gvd_reach, with AOS_E_STATE under the same conditions. opts =
+ * NULL is {0}. AOS_E_INVALID: a null ctx or out, a grid without info, every grid and info case of aos_gvd_clearance,
+ * n_sources negative or above 2^20, a null sources_xy behind a positive count. width * height = 0: status 0, nothing
+ * launched, the counts 0, width_device NULL, every node value 0.
+ * The field is the unique fixed point of width[c] = max(width[c], min(width[n], bottleneck(n -> c))) over the moves
+ * with width = cap at the kept source cells, computed in rounds (n_rounds: the rounds in which some tile ran).
+ * opts.max_rounds works as in aos_gvd_reach: > 0, at most that many rounds are issued, and if a tile still ran in the
+ * last of them the call fails with AOS_E_STATE, "width did not converge in N rounds", and leaves no field behind.
+ * Every call recomputes its field; the outputs are library-owned and valid until the next aos_gvd_width on the handle
+ * or aos_destroy. The state is the call's own: the fields and outputs of earlier aos_gvd_clearance, aos_gvd_regions,
+ * aos_gvd_reach, aos_reach_descend and aos_reach_pull calls stay valid across it, and it stays valid across them.
+ * With w = width at a start cell, aos_gvd_reach(min_d2 = w) followed by aos_reach_pull(start) is the widest route and
+ * its waypoints.
+ * ------------------------------------------------------------------------------------------- */
+#define AOS_WIDTH_NONE 0u
+typedef struct aos_width_opts {
+    int32_t max_rounds;     /* <= 0: no limit                                                                      */
+} aos_width_opts;
+typedef struct aos_width_out {
+    aos_grid_info info;
+    uint64_t n_free, n_reached;
+    int32_t n_sources_used;
+    uint32_t min_width, max_width;                   /* over the reached cells; 0 if n_reached == 0            */
+    const uint32_t *width_device;                    /* width * height words on the handle's GPU               */
+    int32_t num_nodes;
+    const uint32_t *node_width;                      /* host, library-owned                                    */
+    const float *node_radius_m;
+    int32_t n_rounds;                                /* diagnostics, not part of the definition                */
+    uint64_t n_tile_runs;                            /* tile workgroups that ran, over all rounds              */
+    float ms_field, ms_wave, ms_graph;               /* device time: the distance field, cap and seeding / the
+                                                        rounds / statistics, sampling                          */
+} aos_width_out;
+int aos_gvd_width(aos_ctx *ctx, const aos_path_graph *graph, const int8_t *grid, int grid_on_device,
+                  const aos_grid_info *info, const double *sources_xy, int32_t n_sources, const aos_width_opts *opts,
+                  aos_width_out *out);
+/* The last aos_gvd_width's field copied to host memory. AOS_E_STATE before any field exists; AOS_E_INVALID for a
+ * capacity_cells below width * height or a null dst behind cells. */
+int aos_width_field_copy(aos_ctx *ctx, uint32_t *dst, uint64_t capacity_cells);
+/* width and radius_m of n points (x, y) against the last aos_gvd_width's field, by the node rule. Either output may be
+ * null. AOS_E_STATE before any field exists; AOS_E_INVALID for a negative n or a null xy behind a positive n. */
+int aos_width_points(aos_ctx *ctx, const double *xy, int32_t n, uint32_t *width, float *radius_m);
+
 /* Diagnostics: copy an internal device grid of the last frame to host as int8 {0,100}.
  * which: "raster", "inflated", "opened", "skeleton_frameless". */
 int aos_debug_grid(aos_ctx *ctx, const char *which, int8_t *dst, uint64_t capacity);
