@@ -193,6 +193,16 @@ class WidthOut(ctypes.Structure):
 WIDTH_NONE = 0
 
 
+class SoftOpts(ctypes.Structure):
+    _fields_ = [("min_d2", c_u), ("soft_cells", c_i), ("gain", c_i), ("max_rounds", c_i)]
+
+
+class SoftOut(ctypes.Structure):
+    _fields_ = [("info", GridInfo), ("n_passable", c_u64), ("n_reached", c_u64), ("n_soft", c_u64), ("n_sources_used", c_i),
+                ("max_cost", c_u), ("max_weight", c_u), ("cost_device", c_vp), ("num_nodes", c_i), ("node_cost", P(c_u)),
+                ("n_rounds", c_i), ("n_tile_runs", c_u64), ("ms_mask", c_f), ("ms_wave", c_f), ("ms_graph", c_f)]
+
+
 def path_query(initial_waypoint_reached=True, initial_waypoint=(8.0, 0.0), target=-1, saved_target=None, previous=-1,
                current=None, exploration_completed=False) -> PathQuery:
     """aos_path_gen_node state when a graph arrives (aos_path_query)."""
@@ -338,6 +348,10 @@ def lib():
         L.aos_gvd_width.argtypes = [c_vp, P(PathGraph), c_vp, c_i, P(GridInfo), c_vp, c_i, P(WidthOpts), P(WidthOut)]
         L.aos_width_field_copy.argtypes = [c_vp, c_vp, c_u64]
         L.aos_width_points.argtypes = [c_vp, c_vp, c_i, c_vp, c_vp]
+        L.aos_gvd_soft.argtypes = [c_vp, P(PathGraph), c_vp, c_i, P(GridInfo), c_vp, c_i, P(SoftOpts), P(SoftOut)]
+        L.aos_soft_field_copy.argtypes = [c_vp, c_vp, c_u64]
+        L.aos_soft_points.argtypes = [c_vp, c_vp, c_i, c_vp]
+        L.aos_soft_descend.argtypes = [c_vp, c_vp, c_vp, c_vp, c_u64, P(c_u64), P(c_u)]
         L.aos_group_create.argtypes = [P(Params), P(c_i), c_i, c_i, P(c_vp)]
         L.aos_group_destroy.argtypes = [c_vp]
         L.aos_group_set_polygon.argtypes = [c_vp, c_vp, c_u]
@@ -867,6 +881,70 @@ class Ctx:
         _check(lib().aos_width_points(self.h, a.ctypes.data if n else None, n, w.ctypes.data if n else None,
                                       r.ctypes.data if n else None))
         return w, r
+
+    def gvd_soft(self, sources, graph: dict | None = None, grid=None, info: dict | None = None, on_device: bool = False,
+                 min_d2: int = 0, soft_cells: int = 0, gain: int = 0, max_rounds: int = 0) -> dict:
+        """The cost-to-go field of `grid` from the world points `sources` (n, 2) that pays for driving close to
+        obstacles (aos_gvd_soft): gvd_reach's moves, each 5 or 7 times the largest weight 1 + gain * max(0, soft_cells -
+        floor(sqrt(d2))) over the cells it touches, and the costs at the graph's nodes. graph, grid, info, on_device,
+        min_d2 and max_rounds as in gvd_reach."""
+        gs, keep = None, []
+        if graph is not None:
+            nodes = np.ascontiguousarray(graph["nodes"], dtype=np.float64).reshape(-1)
+            gs = PathGraph()
+            gs.num_nodes, gs.nodes_xy = nodes.size // 2, nodes.ctypes.data_as(P(c_d))
+            keep.append(nodes)
+        gi, gp = None, None
+        if grid is not None:
+            gi = GridInfo(info["origin"][0], info["origin"][1], info["resolution"], info["width"], info["height"])
+            if on_device:
+                gp = c_vp(int(grid))
+            else:
+                keep.append(np.ascontiguousarray(grid, dtype=np.int8).reshape(-1))
+                gp = c_vp(keep[-1].ctypes.data or 1)   # (an empty grid is still a grid, not the NULL form)
+        src = np.ascontiguousarray(sources, dtype=np.float64).reshape(-1, 2)
+        opts = SoftOpts(int(min_d2), int(soft_cells), int(gain), int(max_rounds))
+        o = SoftOut()
+        _check(lib().aos_gvd_soft(self.h, ctypes.byref(gs) if gs is not None else None, gp, int(on_device),
+                                  ctypes.byref(gi) if gi is not None else None, src.ctypes.data if len(src) else None,
+                                  len(src), ctypes.byref(opts), ctypes.byref(o)))
+        del keep
+        self._soft_shape = (o.info.height, o.info.width)
+        return {"origin": (o.info.origin_x, o.info.origin_y), "resolution": o.info.resolution, "width": o.info.width,
+                "height": o.info.height, "n_passable": o.n_passable, "n_reached": o.n_reached, "n_soft": o.n_soft,
+                "n_sources_used": o.n_sources_used, "max_cost": o.max_cost, "max_weight": o.max_weight,
+                "cost_device": o.cost_device, "node_cost": _arr(o.node_cost, o.num_nodes, np.uint32),
+                "n_rounds": o.n_rounds, "n_tile_runs": o.n_tile_runs,
+                "ms": {"mask": o.ms_mask, "wave": o.ms_wave, "graph": o.ms_graph}}
+
+    def soft_field(self) -> np.ndarray:
+        """The last gvd_soft's field as a (height, width) uint32 array (aos_soft_field_copy)."""
+        out = np.empty(getattr(self, "_soft_shape", (0, 0)), np.uint32)
+        _check(lib().aos_soft_field_copy(self.h, out.ctypes.data or None, out.size))
+        return out
+
+    def soft_points(self, xy) -> np.ndarray:
+        """The costs of points (n, 2) against the last gvd_soft's field (aos_soft_points)."""
+        a = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        n = len(a)
+        cost = np.empty(n, np.uint32)
+        _check(lib().aos_soft_points(self.h, a.ctypes.data if n else None, n, cost.ctypes.data if n else None))
+        return cost
+
+    def soft_descend(self, start, capacity: int | None = None) -> dict:
+        """The descent from the world point `start` on the last gvd_soft's field (aos_soft_descend): "cells" (linear
+        indices), "xy" (their centres), "n_cells", the full length, and "plain_cost", the sum of 5 and 7 over all its
+        moves. capacity None: room for the whole descent (asked for first); else at most that many cells are returned."""
+        s = np.ascontiguousarray(start, dtype=np.float64).reshape(2)
+        n, plain = c_u64(0), c_u(0)
+        if capacity is None:
+            _check(lib().aos_soft_descend(self.h, s.ctypes.data, None, None, 0, ctypes.byref(n), None))
+            capacity = n.value
+        cells, xy = np.empty(capacity, np.uint32), np.empty((capacity, 2), np.float64)
+        _check(lib().aos_soft_descend(self.h, s.ctypes.data, cells.ctypes.data if capacity else None,
+                                      xy.ctypes.data if capacity else None, capacity, ctypes.byref(n), ctypes.byref(plain)))
+        k = min(capacity, n.value)
+        return {"cells": cells[:k], "xy": xy[:k], "n_cells": n.value, "plain_cost": plain.value}
 
     def cloud_prefetch(self, cloud, n_points: int | None = None, point_step=16, offs=(0, 4, 8), is_dense=True) -> None:
         """Start uploading a host PointCloud2 for the next seedgen() of the same array (aos_cloud_prefetch)."""

@@ -3,8 +3,9 @@
 // Methods by file: seedgen.hip the frame (release, run_seedgen*, the thinning driver, the grid copies, finish_frame,
 // debug_grid); cloud_upload.hip the cloud upload, the prefetch and the streaming map's ingest; ror_stage.hip the
 // ROR stage; tiled.hip the tiled frame; gvd_handle.hip the GVD and the planner calls' graph and grid (plan_graph,
-// plan_grid); path.hip the planner (linearize.hip, clearance.hip, regions.hip, reach.hip and width.hip have no method:
-// their states are the OwnedState members lin_state, clear_state, regions_state, reach_state and width_state).
+// plan_grid); path.hip the planner (linearize.hip, clearance.hip, regions.hip, reach.hip, width.hip and soft.hip have no
+// method: their states are the OwnedState members lin_state, clear_state, regions_state, reach_state, width_state and
+// soft_state).
 #pragma once
 #include <array>
 #include <condition_variable>
@@ -228,7 +229,7 @@ struct aos_ctx {
     bool gvd_async_wait(bool rethrow);   // aos_gvd_wait: collect the oldest job; false if none
     void gvd_view_settle();              // markers / planning: settle which result is current
     // The planner calls' inputs, from their arguments or from the current result (aos_path_plan, aos_gvd_clearance,
-    // aos_gvd_regions, aos_gvd_reach, aos_gvd_width; each settles by its own rule first). graph null: the handle's own graph, with (key, gen) for
+    // aos_gvd_regions, aos_gvd_reach, aos_gvd_width, aos_gvd_soft; each settles by its own rule first). graph null: the handle's own graph, with (key, gen) for
     // the planner's graph cache; throws without one. grid null: the current result's skeleton; a host grid is copied
     // into staging on the handle's stream.
     struct PlanGraph { aos_path_graph g; const void *key; uint64_t gen; };
@@ -243,8 +244,9 @@ struct aos_ctx {
     // ---- the planner calls' states, each defined in its file and created on first use: path planning (path.hip:
     // PathState), /aos/path -> /plan (linearize.hip: LinState), the distance field and GvdGraph clearances
     // (clearance.hip: ClearState), nearest-obstacle regions and the grid GVD ridge (regions.hip: RegionsState), the
-    // clearance-limited cost-to-go field (reach.hip: ReachState), the widest-robot field (width.hip: WidthState)
-    aos::OwnedState path_state, lin_state, clear_state, regions_state, reach_state, width_state;
+    // clearance-limited cost-to-go field (reach.hip: ReachState), the widest-robot field (width.hip: WidthState), the
+    // clearance-weighted cost-to-go field (soft.hip: SoftState)
+    aos::OwnedState path_state, lin_state, clear_state, regions_state, reach_state, width_state, soft_state;
 
     // ---- cloud upload, prefetch and streaming map ingest (cloud_upload.hip)
     void set_cloud(const aos_cloud_view &v);

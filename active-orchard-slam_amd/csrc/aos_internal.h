@@ -111,7 +111,7 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
-// A state that one file defines and the handle owns (PathState, LinState, ClearState, RegionsState, ReachState, WidthState): get<T>()
+// A state that one file defines and the handle owns (PathState, LinState, ClearState, RegionsState, ReachState, WidthState, SoftState): get<T>()
 // creates it on first use and sets the deleter with it, so aos_ctx needs no declaration of T.
 struct OwnedState {
     void *p = nullptr;

@@ -774,6 +774,85 @@ int aos_width_field_copy(aos_ctx *ctx, uint32_t *dst, uint64_t capacity_cells);
  * null. AOS_E_STATE before any field exists; AOS_E_INVALID for a negative n or a null xy behind a positive n. */
 int aos_width_points(aos_ctx *ctx, const double *xy, int32_t n, uint32_t *width, float *radius_m);
 
+/* ---------------------------------------------------------------------------------------------
+ * Cost-to-go that pays for driving close to obstacles. A shortest path under a hard clearance (aos_gvd_reach) runs
+ * along the obstacles' inflation rim; aos_gvd_soft is reach's field with a weight per cell that rises towards the
+ * obstacles, so its descent leaves the rim where the detour is cheap and squeezes through where it is not: the
+ * costmap-weighted plan. Every quantity is an integer: the definitions below fix every word of the result.
+ *  - Grid, cell rule, info and graph checks: aos_gvd_clearance's. Passable: aos_gvd_reach's rule, the byte is not 100
+ *    and d2 >= opts.min_d2 (AOS_D2_NONE counts as >= anything). n_passable = the passable cells.
+ *  - Weight: r[c] = floor(sqrt(d2[c])), the exact integer square root of aos_gvd_clearance's field; pen[c] =
+ *    max(0, soft_cells - r[c]), and 0 where d2[c] is AOS_D2_NONE; wt[c] = 1 + gain * pen[c] on passable cells.
+ *    0 <= soft_cells <= 255, 0 <= gain <= 254, and 1 + gain * max(0, soft_cells - 1) <= 255: a free cell has r >= 1,
+ *    so wt fits a byte. With soft_cells <= 1 or gain == 0 every weight is 1, and then no distance field is computed
+ *    unless min_d2 >= 2. n_soft = the passable cells with wt > 1; max_weight = the largest wt over the passable
+ *    cells, 0 if there are none.
+ *  - Moves: aos_gvd_reach's, to an 8-neighbour inside the grid, no corner cutting. A move a -> b costs base * the
+ *    largest wt over the cells it touches, base 5 (axis) or 7 (diagonal); an axis move touches a and b, a diagonal
+ *    move a, b and the two cells beside the diagonal (the set T(a, b) of aos_reach_sight, the cells whose least
+ *    clearance is aos_gvd_width's bottleneck). The relation is symmetric; with all weights 1 the cost is reach's.
+ *  - Sources: as aos_gvd_reach, 0 <= n_sources <= 2^20 world points; a source that is not finite, has no cell or falls
+ *    on an impassable cell is dropped. n_sources_used = the sources kept (duplicates count).
+ *  - Cost: cost[c], uint32 = the least sum of move costs from a kept source cell to c; 0 at a source cell;
+ *    AOS_COST_NONE at an impassable cell and at a passable cell that no source reaches. n_reached = the cells with a
+ *    finite cost; max_cost = the largest finite cost, AOS_COST_NONE if n_reached == 0.
+ *  - Bound: a least-cost path visits no cell twice, so every finite cost is below 7 * max_weight * n_passable. If that
+ *    product is >= 2^31 the call fails with AOS_E_INVALID, the message names both factors, and no field is left
+ *    behind. With all weights 1 this is reach's own bound (width * height <= 2^28).
+ *  - Nodes and points: the cost at the node's or point's cell by the node rule, AOS_COST_NONE without a cell. No
+ *    metres are given: a weighted cost is not a length.
+ *  - Descent: aos_gvd_reach's rule with this call's move costs: from cell c the first neighbour n, in reach's order
+ *    of the eight moves, that an allowed move reaches with cost[n] + w(c, n) == cost[c]; down to the first cell of
+ *    cost 0; at most cost / 5 + 1 cells. plain_cost = the sum of 5 and 7 over the descent's moves (host arithmetic on
+ *    the cells): beside reach's cost at the same start it is the length of the detour paid for clearance.
+ * graph and grid = NULL are the handle's own, as in aos_gvd_reach, with AOS_E_STATE under the same conditions. opts =
+ * NULL is {0, 0, 0, 0}. AOS_E_INVALID: reach's cases, soft_cells or gain out of range, a weight above 255, and the
+ * bound above. width * height = 0: status 0, nothing launched, the counts 0, max_cost AOS_COST_NONE, cost_device NULL,
+ * every node value AOS_COST_NONE.
+ * The field is the unique fixed point of cost[c] = min(cost[c], cost[n] + w(n, c)) over the moves, computed in rounds
+ * as reach's (n_rounds: the rounds in which some tile ran). opts.max_rounds > 0: at most that many rounds are issued,
+ * and if a tile still ran in the last of them the call fails with AOS_E_STATE, "soft did not converge in N rounds",
+ * and leaves no field behind. Every call recomputes its field; the outputs are library-owned and valid until the next
+ * aos_gvd_soft on the handle or aos_destroy. The state is the call's own: the fields and outputs of aos_gvd_clearance,
+ * aos_gvd_regions, aos_gvd_reach, aos_reach_descend, aos_reach_pull and aos_gvd_width stay valid across it, and it
+ * stays valid across them; aos_reach_sight and aos_reach_pull stay bound to the last aos_gvd_reach's mask. No pull is
+ * offered for soft descents: pulling a descent taut undoes the centring it paid for.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct aos_soft_opts {
+    uint32_t min_d2;        /* a passable cell's d2 is at least this (<= 1: every free cell is passable)          */
+    int32_t soft_cells;     /* cells nearer than this to an obstacle (r < soft_cells) weigh more; 0..255           */
+    int32_t gain;           /* weight per cell of that nearness; 0..254                                            */
+    int32_t max_rounds;     /* <= 0: no limit                                                                      */
+} aos_soft_opts;
+typedef struct aos_soft_out {
+    aos_grid_info info;
+    uint64_t n_passable, n_reached, n_soft;
+    int32_t n_sources_used;
+    uint32_t max_cost, max_weight;                   /* AOS_COST_NONE if n_reached == 0; 0 if n_passable == 0  */
+    const uint32_t *cost_device;                     /* width * height words on the handle's GPU               */
+    int32_t num_nodes;
+    const uint32_t *node_cost;                       /* host, library-owned                                    */
+    int32_t n_rounds;                                /* diagnostics, not part of the definition                */
+    uint64_t n_tile_runs;                            /* tile workgroups that ran, over all rounds              */
+    float ms_mask, ms_wave, ms_graph;                /* device time: distance field, weights and seeding / the
+                                                        rounds / statistics, sampling                          */
+} aos_soft_out;
+int aos_gvd_soft(aos_ctx *ctx, const aos_path_graph *graph, const int8_t *grid, int grid_on_device,
+                 const aos_grid_info *info, const double *sources_xy, int32_t n_sources, const aos_soft_opts *opts,
+                 aos_soft_out *out);
+/* The last aos_gvd_soft's field copied to host memory. AOS_E_STATE before any field exists; AOS_E_INVALID for a
+ * capacity_cells below width * height or a null dst behind cells. */
+int aos_soft_field_copy(aos_ctx *ctx, uint32_t *dst, uint64_t capacity_cells);
+/* The cost of n points (x, y) against the last aos_gvd_soft's field, by the node rule. AOS_E_STATE before any field
+ * exists; AOS_E_INVALID for a negative n or a null xy behind a positive n. */
+int aos_soft_points(aos_ctx *ctx, const double *xy, int32_t n, uint32_t *cost);
+/* The descent from start_xy on the last aos_gvd_soft's field: the cells' linear indices into cells and, if xy is not
+ * null, their centres into xy; at most capacity_cells of them are written, and *n_cells is always the full length.
+ * *plain_cost (may be NULL) is summed over the full descent whatever the capacity, 0 for an empty one. AOS_E_STATE
+ * before any field exists; AOS_E_INVALID for a null start_xy or n_cells, or a null cells behind a capacity above 0. */
+int aos_soft_descend(aos_ctx *ctx, const double start_xy[2], uint32_t *cells, double *xy, uint64_t capacity_cells,
+                     uint64_t *n_cells, uint32_t *plain_cost);
+
 /* Diagnostics: copy an internal device grid of the last frame to host as int8 {0,100}.
  * which: "raster", "inflated", "opened", "skeleton_frameless". */
 int aos_debug_grid(aos_ctx *ctx, const char *which, int8_t *dst, uint64_t capacity);
